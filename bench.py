@@ -1,6 +1,12 @@
 """Benchmark: CIND-discovery triples/s on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--scale 1.0] [--scaling weak|strong]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it draws the seeded input, warms up, times the K steps, writes the
+last step's hand-over when --dump-outputs is given, and prints the line.  Every other leg described below (the
+`device_resident` repeat, `cpu_baseline`, `ingest`, `c4_strong`) runs only with --full, where its own switches
+(--no-resident, --no-cpu-baseline, --no-ingest, --c4-strong) still apply; in a plain run their fields are null or absent.
 
 A *step* is T_disc of SURVEY.md 8(d) / BASELINE.md 2 over one batch: from dictionary-encoded triples resident
 in HBM to CIND id-records in host memory.  rdf_run = frequent conditions -> capture groups -> CIND extraction +
@@ -32,6 +38,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 
@@ -224,6 +231,50 @@ def layout_bytes(L, heavy_chunks=0):
             8 * L["n_members"] + 8 * L["n_captures"] + 20 * heavy_chunks)
 
 
+DUMP_BUDGET = 60 << 20  # payload bytes --dump-outputs writes at most (float64; the .npy headers stay within 64 MB)
+
+
+def handover_arrays(sink, L):
+    """What the caller of the last timed step holds: the parts of the compact result in the sink's host buffers, cut to
+    the layout's element counts, and the heavy-bits chunks.  (Streamed refs: the last chunk; paged: the last page.)"""
+    from rdfind_amd import _lib
+
+    def view(b):
+        return b.array if isinstance(b, _lib.PinnedBuffer) else b
+
+    out = {}
+    for name, _, count in _lib.COMPACT_PARTS:
+        n = count(L)
+        if name == "refs" and n > sink.cap["refs"]:
+            n = n % sink.cap["refs"] or sink.cap["refs"]
+        out[name] = view(sink._keep[name])[:n]
+    for name in ("deps", "pos", "bits") if sink.heavy_chunks else ():
+        out["heavy_" + name] = view(sink.heavy[name])[:sink.heavy_chunks]
+    return out
+
+
+def dump_outputs(path, arrays, layout, suffix=""):
+    """DIR/<name>.npy in float64: u32 parts element for element, u64 parts as (low, high) u32 pairs, so every id
+    is exact.  Parts are written whole while they fit an equal share of DUMP_BUDGET (smallest first, the rest of a
+    share passing on); a larger part is a fixed seeded sample of its rows, in row order."""
+    os.makedirs(path, exist_ok=True)
+    rows = {k: (a.view(np.uint32).reshape(-1, 2) if a.dtype.itemsize == 8 else a) for k, a in arrays.items()}
+    full = {k: 8 * r.size for k, r in rows.items()}
+    remaining, left = DUMP_BUDGET, len(rows)
+    for name in sorted(rows, key=lambda k: (full[k], k)):
+        r = rows[name]
+        share = remaining // left
+        if full[name] > share:
+            keep = share // (8 * (r.size // len(r)))
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            r = r[np.sort(rng.choice(len(r), size=keep, replace=False))]
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), r.astype(np.float64))
+        remaining -= 8 * r.size
+        left -= 1
+    # the layout's counts (n_cinds, n_refs, n_runs, n_lists, n_list_refs, n_members, n_captures), then the heavy chunks
+    np.save(os.path.join(path, f"layout{suffix}.npy"), np.array(layout, np.float64))
+
+
 def ctx_pages(ctx):
     """Pages of the last paged run (rdf_next_page calls that produced a page)."""
     return getattr(ctx, "_pages", None)
@@ -355,6 +406,12 @@ def main():
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: every GPU holds one config-sized share (N GPUs run the config at N x scale); "
                          "strong: the config at scale is split over the GPUs")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the legs a plain run leaves "
+                    "out: the device-resident repeat, the CPU baseline, the N-Triples ingest and c4_strong")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's hand-over (the sink's host buffers) as "
+                         "DIR/<name>.npy in float64, at most 64 MB in all (a larger part as a fixed seeded sample); with "
+                         "several ranks, rank r > 0 writes <name>.rank<r>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ingest", action="store_true", help="skip the N-Triples ingest leg (rank 0, N=1)")
     ap.add_argument("--cpu-sample-scale", type=float, default=None,
@@ -374,8 +431,8 @@ def main():
     ap.add_argument("--no-numa-bind", action="store_true", help="leave the process on every CPU (default: bound to the "
                     "GPU's NUMA node before any host buffer is allocated, rdfind_amd/numa.py)")
     ap.add_argument("--c4-strong", choices=("auto", "on", "off"), default="auto",
-                    help="also time BASELINE configs[3] (c4, Freebase-shaped, 10^9 triples, support 100) split over the "
-                         "N GPUs (strong scaling; the north-star scaling config) and report it as `c4_strong` (auto: "
+                    help="with --full: also time BASELINE configs[3] (c4, Freebase-shaped, 10^9 triples, support 100) split "
+                         "over the N GPUs (strong scaling; the north-star scaling config) and report it as `c4_strong` (auto: "
                          "when N > 1 with the default c2 workload and the nccl backend)")
     ap.add_argument("--c4-scale", type=float, default=1.0, help="scale of the c4_strong leg (1.0 = 10^9 triples)")
     ap.add_argument("--c4-steps", type=int, default=2)
@@ -518,9 +575,12 @@ def main():
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
     L = ctx.result_layout()
+    if args.dump_outputs and args.steps > 0:
+        dump_outputs(args.dump_outputs, handover_arrays(sink, L), list(L.values()) + [sink.heavy_chunks],
+                     f".rank{rank}" if rank else "")
     # the same steps without the hand-over (results left in HBM): the device-resident rate
     elapsed_dev = None
-    if not args.no_resident:
+    if args.full and not args.no_resident:
         ctx.set_handover()  # results stay in HBM: no early copies either
         barrier()
         t1 = time.perf_counter()
@@ -571,7 +631,7 @@ def main():
     count_roof = {k: dict(fams[k], bound="hbm") for k in ("unary", "binary") if k in fams}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import c_oracle
 
         # the same workload when the streamed C restatement finishes in ~30 s on the box's threads, else a sample
@@ -596,10 +656,11 @@ def main():
     ingest = None
     # one rdf_parse_ntriples call holds < 2^31 term occurrences (its table has 2x as many u32-indexed slots), and the
     # text is built in host memory (~170 B per triple): the ingest leg is for inputs up to 2 * 10^8 triples
-    if rank == 0 and world == 1 and not args.no_ingest and d.n > 200_000_000:
+    want_ingest = args.full and rank == 0 and world == 1 and not args.no_ingest
+    if want_ingest and d.n > 200_000_000:
         ingest = {"skipped": f"{d.n} triples: beyond one parse call's term table (< 2^31 occurrences) and the text's "
                              "host memory; the ingest leg runs up to 2e8 triples"}
-    elif rank == 0 and world == 1 and not args.no_ingest:
+    elif want_ingest:
         # parse/encode timed separately -- the same triples as N-Triples text through
         # rdf_parse_ntriples (ids/terms are checked by tests/)
         tt = d.terms.term
@@ -665,8 +726,8 @@ def main():
                      "classes": cs["n_classes"], "class_cinds": cs["n_class_cinds"],
                      **({"exchange_rank0": getattr(ctx, "x_stats", None)} if world > 1 else {})},
         }
-    want_c4 = args.c4_strong == "on" or (args.c4_strong == "auto" and args.config == "c2"
-                                         and (world == 1 or args.backend == "nccl"))
+    want_c4 = args.full and (args.c4_strong == "on" or (args.c4_strong == "auto" and args.config == "c2"
+                                                        and (world == 1 or args.backend == "nccl")))
     if want_c4:
         if line is not None:  # the main leg's measurement, on record before the c4 leg starts (stderr)
             print("bench.py: main leg: " + json.dumps(line), file=sys.stderr, flush=True)

@@ -968,6 +968,44 @@ def test_early_handover_matches_plain_copy():
         g.close()
 
 
+def test_bench_dump_is_the_handed_over_result(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the files written from the sink's buffers after a step hold that step's compact result,
+    part by part (u64 parts as low/high u32 pairs), the heavy-bits chunks included (c5 sample with lowered heavy
+    columns), also when the registered buffers were filled early (second step into the same sink)."""
+    from bench import CompactSink, dump_outputs, handover_arrays
+
+    counts = {name: count for name, _, count in _lib.COMPACT_PARTS}
+    chunks = 0
+    for cfg, scale, heavy_min in (("c1", 0.05, "64"), ("c5", 0.01, "2")):
+        monkeypatch.setenv("RDFIND_HEAVY_MIN", heavy_min)
+        d = dataset(cfg, scale)
+        g = _lib.Context(0)
+        try:
+            g.set_triples(d.s, d.p, d.o, d.num_terms)
+            g.set_result_form(True)
+            sink = CompactSink(early=True)
+            for _ in range(2):
+                g.run(d.min_support)
+                L = sink.copy(g)
+            dump_outputs(str(tmp_path / cfg), handover_arrays(sink, L), list(L.values()) + [sink.heavy_chunks])
+            plain = g.copy_result_compact()
+            assert sink.heavy_chunks == plain["n_heavy_chunks"]
+            chunks += sink.heavy_chunks
+            names = list(counts) + (["heavy_deps", "heavy_pos", "heavy_bits"] if sink.heavy_chunks else [])
+            for name in names:
+                exp = plain[name][:counts[name](L) if name in counts else sink.heavy_chunks]
+                got = np.load(tmp_path / cfg / f"{name}.npy")
+                assert got.dtype == np.float64
+                if exp.dtype == np.uint64:
+                    got = got[:, 0].astype(np.uint64) | (got[:, 1].astype(np.uint64) << np.uint64(32))
+                assert np.array_equal(got.astype(exp.dtype), exp), (cfg, name)
+            layout = np.load(tmp_path / cfg / "layout.npy").tolist()
+            assert layout == [float(v) for v in L.values()] + [float(sink.heavy_chunks)]
+        finally:
+            g.close()
+    assert chunks > 0  # the heavy-bits parts were written
+
+
 @pytest.mark.parametrize("dedup,dup_min", [("0", "256"), ("1", "1"), ("1", "256")])
 def test_light_dedup_parity(monkeypatch, dedup, dup_min):
     """Light dependents with identical group lists verified once per class (RDFIND_LIGHT_DEDUP=1; members take their
