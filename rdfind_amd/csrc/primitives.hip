@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "primitives.hpp"
+#include "switches.hpp"
 
 namespace rdf {
 
@@ -809,7 +810,7 @@ hipError_t radix_partition_hashed(Workspace& ws, u64*& keys, u64*& tmp, u64 n, i
     const u32 tiles = (u32)((n + RS_TILE - 1) / RS_TILE);
     // digits of <= 9 bits (c4 at 10^9 triples: 20 bits in 3 passes 89.6 ms of K2, in 2 passes of 10 bits 96.0 ms: a
     // 1,024-bin digit leaves ~4 keys per bin of a tile; RDFIND_PART_DIGIT overrides, 8..10)
-    static const int pdig = getenv("RDFIND_PART_DIGIT") ? std::max(8, std::min(10, atoi(getenv("RDFIND_PART_DIGIT")))) : 9;
+    const int pdig = proc_switches().part_digit;
     const int passes = (bits + pdig - 1) / pdig;
     u32* hist = (u32*)ws.scratch(((u64)hist_stride(tiles) << 10) * sizeof(u32), 1);
     if (!hist) return hipErrorOutOfMemory;

@@ -14,28 +14,155 @@
 #include "../../include/rdfind_hip.h"
 #include "primitives.hpp"
 #include "kernels.inl"
+#include "switches.hpp"
 
 using namespace rdf;
 
 #define RDF_VERSION "rdfind_amd 0.1 (gfx950)"
 
-struct rdf_ctx {
+// Every device buffer of a context, declared once: B(lifetime class, name).  The fields of CtxBuffers (a base of rdf_ctx,
+// so c->rec and ENSURE(c, rec, ...) name them), their iteration (for_each_buf: destroy, rdf_device_bytes, the memory
+// report) and the release lists all come from this table.  Lifetime classes:
+//   INPUT         the resident input, its dictionary and the parsed text: kept until the context is destroyed
+//   PARSE         scratch of rdf_parse_ntriples, released when it returns
+//   SPARE_FC      the frequent-condition stage's record scratch, spare once that stage is done (reclaim_spare)
+//   SPARE_GROUPS  the group build's record and sort buffers, spare once the groups are built
+//   SPARE_X       the exchange buffers, spare from the routing of the triples to the end of the group build
+//   RUN           everything else: per-run state, released with the three SPARE classes by rdf_release_scratch and
+//                 when a new input finds the context holding too much (release_run_buffers)
+// clang-format off
+#define RDF_CTX_BUFFERS(B) \
+    /* device scalars (pinned host mirrors: hscal, hread) */ \
+    B(INPUT, scal) \
+    /* triples */ \
+    B(INPUT, ts) B(INPUT, tp) B(INPUT, to) \
+    /* --distinct-triples: slot table, keep flags, positions, compacted copy (swapped with ts / tp / to) */ \
+    B(RUN, dtab) B(RUN, dkeep) B(RUN, dpos) B(RUN, xs) B(RUN, xp) B(RUN, xo) \
+    /* N-Triples ingest: the text and the term table (rdf_set_dictionary_parsed, rdf_copy_terms, sharded ingest) ... */ \
+    B(INPUT, ntext) B(INPUT, nterm_off) B(INPUT, nterm_len) \
+    /* ... line / term arrays, dictionary table (~36 B per term occurrence + the slot table) */ \
+    B(PARSE, ncnt) B(PARSE, ncoff) B(PARSE, nlstart) B(PARSE, ntstart) B(PARSE, ntlen) B(PARSE, nvalid) B(PARSE, nlpos) \
+    B(PARSE, nhv) B(PARSE, nslot) B(PARSE, ntab) B(PARSE, nrep) B(PARSE, nfirst) B(PARSE, nfid) \
+    /* frequent conditions */ \
+    B(RUN, frank) B(RUN, fval) B(RUN, fext) \
+    B(RUN, cnt) B(SPARE_FC, tkeys) B(RUN, tcnt) B(RUN, bkeys) B(RUN, bkeys_tmp) B(RUN, lkeys) B(RUN, lvals) B(RUN, flags) \
+    B(RUN, pos) \
+    /* partitioned K1 / K2 (counts.inl) */ \
+    B(RUN, uhist) B(SPARE_FC, urecs) B(RUN, usl) B(RUN, cntg) B(RUN, fstage) B(RUN, bfreq) B(RUN, boff) B(RUN, fbits) \
+    B(SPARE_FC, brkeys) \
+    /* K2 records re-partitioned into sub-buckets (k_b2_split) and their starts */ \
+    B(SPARE_FC, brkeys2) B(RUN, bstart2) \
+    /* --use-ars: triple counts of the frequent unary | binary conditions, rules (5 u32 each), unary dependent -> */ \
+    /* implied ref */ \
+    B(RUN, arcnt) B(RUN, ar_bits) B(RUN, ar_rules) B(RUN, arref) \
+    /* capture groups */ \
+    B(SPARE_GROUPS, rec) B(SPARE_GROUPS, rec_tmp) B(RUN, support) B(RUN, fidx) B(RUN, fcap) B(RUN, info) \
+    B(SPARE_GROUPS, fk) B(SPARE_GROUPS, fk_tmp) B(RUN, fpos) B(RUN, cstart) B(RUN, skip) B(RUN, gflag) B(RUN, gexcl) \
+    B(RUN, goff) B(RUN, gcap) B(RUN, gmap) B(RUN, csup) B(RUN, doff) B(RUN, dcur) B(RUN, dgrp) \
+    B(RUN, hist) B(RUN, heavy_list) B(RUN, hbit) B(RUN, bcomp) B(RUN, bkeyc) B(RUN, pcnt) B(RUN, poff) B(RUN, pcur) \
+    B(RUN, plist) \
+    /* capture groups built in join-value ranges (g_build_ranges); jbh: the emission blocks' join-bucket histograms */ \
+    /* (k_emit_join_bhist); lsup: a sharded rank's supports (the all-reduce replaces support) */ \
+    B(RUN, jhist) B(RUN, rsup) B(RUN, offp) B(RUN, jbh) B(RUN, lsup) \
+    /* pass 1's sorted records of every range, kept for pass 2 when they fit next to the range scratch (pass 2 then */ \
+    /* neither re-emits nor re-sorts a range); jrmap: the kept build's ranges' first join values and join buckets; */ \
+    /* ecache: each range's scanned K3 block offsets from its first emission */ \
+    B(SPARE_GROUPS, rstore) B(RUN, jrmap) B(RUN, ecache) \
+    /* light dependents with identical group lists (d_light_dedup): keys, key table, class representatives, counts */ \
+    B(RUN, ukey) B(RUN, utab) B(RUN, urep) B(RUN, ucnt) B(RUN, unoff) B(RUN, uebin) B(RUN, umem) \
+    /* hot join values' owners (open-addressing table), this owner's candidates */ \
+    B(RUN, hot) B(RUN, hotc) \
+    /* cinds */ \
+    B(RUN, pivot) B(RUN, nchl) B(RUN, nchh) B(RUN, choffl) B(RUN, choffh) B(RUN, epairs) B(RUN, epairs_tmp) B(RUN, eoff) \
+    B(RUN, hcounts) B(RUN, hoff) B(RUN, hbits) B(RUN, cbits) B(RUN, hown) B(RUN, cown) B(RUN, sbase) B(RUN, dcls) \
+    B(RUN, crep) B(RUN, out) B(RUN, stage_rows) \
+    /* output formatting (K8); dheap / dtoff: the uploaded dictionary */ \
+    B(INPUT, dheap) B(INPUT, dtoff) B(RUN, cslen) B(RUN, csoff) B(RUN, cstr) B(RUN, flen) B(RUN, floff) B(RUN, fbuf) \
+    /* decoded Cind-shaped rows (rdf_copy_cinds_decoded); per-block partial sums of the pivot statistics */ \
+    B(RUN, drows) B(RUN, ppart) \
+    /* output run table: run r holds refs [runoff[r], runoff[r+1]) of dependent rundep[r] */ \
+    B(RUN, runoff) B(RUN, rundep) \
+    B(RUN, nitl) B(RUN, itoffl) B(RUN, dead) B(RUN, ebin) B(RUN, pseg) B(RUN, psegoff) B(RUN, pbest) B(RUN, pnl) \
+    /* light-group signatures (SIG_W words per compact capture), computed by the pivot pass */ \
+    B(RUN, lsig) \
+    /* group -> size | heavy bit; sum of light group sizes, of their squares (k_group_info) */ \
+    B(RUN, ginfo) B(RUN, gsums) \
+    /* dependent -> second pivot (smallest light group after the pivot); -> the next PIV_EXTRA light groups after it */ \
+    B(RUN, piv2) B(RUN, pivx) \
+    /* dense light groups: group -> bitmap row, row -> group, the bitmaps */ \
+    B(RUN, gdrow) B(RUN, dlist) B(RUN, dbits) \
+    /* k_light's issue order (k_light_long_flags / k_light_order) */ \
+    B(RUN, iflag) B(RUN, iexcl) B(RUN, iorder) \
+    /* classes of dependents with shared ref lists */ \
+    B(RUN, ctab) B(RUN, cflag) B(RUN, ccid) B(RUN, ckeys) B(RUN, ckeys_tmp) B(RUN, coff) B(RUN, cmask) B(RUN, cpiv) \
+    B(RUN, cnch) B(RUN, cchoff) B(RUN, ccnt) B(RUN, lwoff) B(RUN, clists) B(RUN, cself) B(RUN, cmcnt) B(RUN, cobase) \
+    B(RUN, ctiles) B(RUN, ctoff) \
+    /* heavy-only refs in compact form (RDF_FORM_HEAVY_BITS); list offsets of the shared (class) ref lists */ \
+    B(RUN, hpos) B(RUN, loff) \
+    /* paged discovery */ \
+    B(RUN, pedges) B(RUN, pedges_tmp) \
+    /* sharded input: the triples received for this rank's join shard */ \
+    B(RUN, wts) B(RUN, wtp) B(RUN, wto) \
+    B(RUN, item_dep) B(RUN, eblk) B(RUN, lslot) B(RUN, npk) B(RUN, pkoff) B(RUN, pk_dep) B(RUN, nmch) B(RUN, mchoff) \
+    B(RUN, mch_dep) \
+    B(SPARE_X, xsend) B(SPARE_X, xrecv) B(RUN, gbest) B(RUN, nrl) B(RUN, smask) B(RUN, smask_tmp) B(RUN, cpairs) \
+    B(RUN, cpairs_tmp) B(RUN, obounds) \
+    /* holder-first light exchange (sh_phase5 / sh_phase15) */ \
+    B(RUN, lmask) B(RUN, hrep) B(RUN, vpairs) B(RUN, vcoff) B(RUN, vpiv) \
+    /* this rank's binary dependents' final pairs; dependent segments */ \
+    B(RUN, ebown) B(RUN, segb) B(RUN, sege) B(RUN, seglen) \
+    /* light pass B's output slots (pass A's stay in epairs_tmp / lslot) */ \
+    B(RUN, bslots) B(RUN, bcounts) \
+    /* sharded: frequent unary keys (owned, then every rank's, sorted) */ \
+    B(RUN, ukeys) B(RUN, ukeys_tmp) \
+    /* sharded ingest (rdf_shard_parse_begin): local terms routed to their owners, the owner's dictionary, global ids; */ \
+    /* own_text / own_off / own_len: the terms this rank owns (the dictionary of the resident ids) */ \
+    B(RUN, ithv) B(RUN, ikeys) B(RUN, ikeys_tmp) B(RUN, iwords) B(RUN, iwoff) B(RUN, ihdr) B(RUN, ipay) B(RUN, ibnd) \
+    B(RUN, iwb) B(RUN, rhdr) B(RUN, rlen) B(RUN, rwords) B(RUN, rwoff) B(RUN, rts) B(RUN, rhv) B(RUN, rvalid) B(RUN, rtab) \
+    B(RUN, rslot) B(RUN, rrep) B(RUN, rfirst) B(RUN, rfid) B(RUN, rhist) B(RUN, rreply) \
+    B(INPUT, own_text) B(INPUT, own_off) B(INPUT, own_len) B(RUN, gmapv) \
+    /* dictionary by owner lookup */ \
+    B(RUN, dneed) B(RUN, dnpos) B(RUN, dwn) B(RUN, dwo) B(RUN, dhdr) B(RUN, dlen) B(RUN, dlwords) B(RUN, dwoff) B(RUN, tids) \
+    B(RUN, tlenv) B(RUN, toffv) B(RUN, tout)
+// clang-format on
+
+enum BufClass { BUF_INPUT, BUF_PARSE, BUF_SPARE_FC, BUF_SPARE_GROUPS, BUF_SPARE_X, BUF_RUN };
+struct CtxBuffers {
+#define RDF_BUF_FIELD(cls, name) DevBuf name;
+    RDF_CTX_BUFFERS(RDF_BUF_FIELD)
+};
+static const struct BufEntry {
+    const char* name;
+    BufClass cls;
+    DevBuf CtxBuffers::*field;
+} kBufs[] = {
+#define RDF_BUF_ENTRY(cls, name) {#name, BUF_##cls, &CtxBuffers::name},
+    RDF_CTX_BUFFERS(RDF_BUF_ENTRY)
+};
+static_assert(sizeof(CtxBuffers) == sizeof(kBufs) / sizeof(kBufs[0]) * sizeof(DevBuf), "a DevBuf declared outside the table");
+
+// the RDFIND_* switches of a context (switches.hpp), read when it is created
+struct Switches {
+    RDF_CTX_SWITCHES(RDF_SW_FIELD)
+};
+static Switches read_switches() {
+    Switches s;
+    RDF_CTX_SWITCHES(RDF_SW_READ)
+    return s;
+}
+
+struct rdf_ctx : CtxBuffers {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
     Workspace ws;
+    Switches sw;
 
-    // device scalars + pinned host mirror
-    DevBuf scal;
+    // pinned host mirror of the device scalars (scal)
     u64* hscal = nullptr;
     u64* hread = nullptr;   // pinned, device-mapped: k_gather_scalars writes the read-back scalars here directly
     u64* hread_d = nullptr; // its device address
 
-    // triples
-    DevBuf ts, tp, to;
-    DevBuf dtab, dkeep, dpos, xs, xp, xo;  // --distinct-triples: slot table, keep flags, positions, compacted copy
-    // N-Triples ingest: text, line/term arrays, dictionary table, term table
-    DevBuf ntext, ncnt, ncoff, nlstart, ntstart, ntlen, nvalid, nlpos, nhv, nslot, ntab, nrep, nfirst, nfid, nterm_off, nterm_len;
     u64 n_terms_parsed = 0;  // rows of nterm_off/nterm_len (rdf_copy_terms)
     bool parsed_dict = false;  // the resident triples' ids are the last parse's dictionary
     const u32 *s = nullptr, *p = nullptr, *o = nullptr;
@@ -45,56 +172,27 @@ struct rdf_ctx {
 
     // frequent conditions
     u32 ms = 1;
-    DevBuf frank, fval, fext;
     u32 U = 0, Us = 0, Up = 0;
-    DevBuf cnt, tkeys, tcnt, bkeys, bkeys_tmp, lkeys, lvals, flags, pos;
     u64 B = 0, lcap = 0;
     std::vector<u64> h_bkeys;
     bool h_bkeys_valid = false;
-    bool force_global_counts = false;
-    bool allow_hclass = true;
-    u64 heavy_min = 64;  // smaller groups are cheaper to verify by binary search than as bit columns
-    // --use-ars (rdf_association_rules): rules (5 u32 each), per-condition counts, unary dependent -> implied ref
+    // --use-ars (rdf_association_rules)
     bool ar_on = false;
     u64 n_rules = 0;
-    DevBuf arcnt, ar_bits, ar_rules, arref;  // arcnt: triple counts of the frequent unary | binary conditions
 
     // capture groups
-    DevBuf rec, rec_tmp, support, fidx, fcap, info, fk, fk_tmp, fpos, cstart, skip, gflag, gexcl, goff, gcap, gmap, csup, doff, dcur, dgrp;
-    DevBuf hist, heavy_list, hbit, bcomp, bkeyc, pcnt, poff, pcur, plist;
-    DevBuf jhist, rsup, offp;  // capture groups built in join-value ranges (g_build_ranges)
-    DevBuf jbh;                // ... the emission blocks' join-bucket histograms (k_emit_join_bhist)
-    DevBuf lsup;               // sharded join ranges: this rank's supports (the all-reduce replaces c->support)
     struct JoinRange { u32 lo, hi; u64 recs; };
     std::vector<JoinRange> jranges;  // the current build's join ranges (pass 1 -> pass 2)
     u64 jr_cap_rec = 1;              // records of the largest range (the range scratch's size)
-    // pass 1's sorted records of every range, kept for pass 2 when they fit next to the range scratch (pass 2 then
-    // neither re-emits nor re-sorts a range); RDFIND_RANGE_KEEP=0: always re-emit
-    DevBuf rstore;
     std::vector<u64> jr_seg, jr_J;   // range k's slots in rstore start at jr_seg[k]; its sorted records
-    bool jr_keep = false, range_keep = true;
+    bool jr_keep = false;            // pass 2 reads pass 1's records from rstore (g_range_keep_plan)
     u64 peak_bytes = 0;              // RDFIND_MEM_REPORT: the largest sum of the buffers' sizes so far
-    DevBuf jrmap;                    // the kept range build: the ranges' first join values and first join buckets
-    // light dependents with identical group lists (d_light_dedup): keys, key table, class representatives, counts
-    DevBuf ukey, utab, urep, ucnt, unoff, uebin, umem;
-    u32 dup_min = 256;               // RDFIND_DUP_MIN: the shortest group list that looks for an equal one
-    u64 u1_radix_min = 0;            // RDFIND_U1_RADIX_MIN: 3n from which K1 takes its radix form (0: the rule)
-    int light_dedup = -1;            // RDFIND_LIGHT_DEDUP: 0 every light dependent verified on its own, 1 once per class
-                                     // of equal group lists, unset: classes where the light pass stages (c2-like inputs)
     u64 n_dedup_members = 0;         // light dependents that took their representative's refs (last discovery)
     bool dedup_pending = false;      // d_light_dedup ran: d_dedup_expand reads the member count
     bool sh_ranged = false;          // the sharded build of this run goes in join ranges (sh_phase14 -> sh_phase1)
     u64 sh_m = 0;                    // sharded: triples received for this rank's join shard (wts / wtp / wto)
-    std::string test_fail_launch;    // RDFIND_TEST_FAIL_LAUNCH: a kernel launched with an invalid configuration (test hook)
-    bool test_oom_discovery = false; // RDFIND_TEST_OOM_DISCOVERY: rdf_discover_cinds fails with RDF_ERR_OOM (test hook)
-    int test_fail_rank = -1, test_fail_phase = -1;  // RDFIND_TEST_FAIL_SHARD=rank:phase: that rank's rdf_shard_step fails
-                                                    // with RDF_ERR_OOM at that phase (test hook: cross-rank failure agreement)
-    int holder_qbits = 2;            // RDFIND_HOLDER_Q: pivot-holder election on log-size buckets (holder_key; 0: exact)
-    bool hot_balance = true;         // RDFIND_HOT_BALANCE=0: every join value's owner by hash (no hot table)
-    DevBuf hot, hotc;                // hot join values' owners (open-addressing table), this owner's candidates
-    u32 hot_mask = 0;                // table slots - 1 (0 with hot_n == 0: no table)
+    u32 hot_mask = 0;                // hot table slots - 1 (0 with hot_n == 0: no table)
     u64 hot_n = 0, sh_Bu = 0;        // hot values in the table; this owner's frequent unary keys (phase 16 -> 18)
-    u64 group_range_records = 0;  // RDFIND_GROUP_RANGE test hook: records per join range (0: automatic)
     u64 n_group_ranges = 1;
     u64 J = 0, Jf = 0, G = 0, J_emit = 0;  // J: distinct-within-iteration records sorted; J_emit: records emitted
     u32 C = 0, Cu = 0, nheavy = 0;
@@ -103,28 +201,14 @@ struct rdf_ctx {
     u64 *rec_sorted = nullptr;
 
     // cinds
-    DevBuf pivot, nchl, nchh, choffl, choffh, epairs, epairs_tmp, eoff, hcounts, hoff, hbits, cbits, hown, cown, sbase, dcls, crep, out, stage_rows;
-    DevBuf dheap, dtoff, cslen, csoff, cstr, flen, floff, fbuf;  // output formatting (K8)
     u64 dict_terms = 0, run_id = 0, capstr_run = ~0ull;
-    DevBuf drows;           // decoded Cind-shaped rows (rdf_copy_cinds_decoded)
-    DevBuf ppart;           // per-block partial sums of the pivot statistics
-    DevBuf runoff, rundep;  // output run table: run r holds refs [runoff[r], runoff[r+1]) of dependent rundep[r]
-    DevBuf nitl, itoffl, dead, ebin, pseg, psegoff, pbest, pnl;
-    DevBuf lsig;          // light-group signatures (SIG_W words per compact capture), computed by the pivot pass
-    DevBuf brkeys2, bstart2;  // K2 records re-partitioned into sub-buckets (k_b2_split) and their starts
-    DevBuf ginfo;  // group -> size | heavy bit (k_group_info)
-    DevBuf gsums;  // sum of light group sizes, of their squares (k_group_info)
     bool light_stage = false;  // k_light_stage: stage small light groups in LDS rows (chosen per run)
     bool light_hiocc = false;  // k_light_plain_hi: the plain variant at 6 waves per SIMD (LIGHT_HIOCC_*)
     u64 light_wmean = 0;       // member-weighted mean light group size of the run (k_group_info sums)
-    DevBuf piv2;   // dependent -> second pivot (smallest light group after the pivot)
-    DevBuf pivx;   // dependent -> the next PIV_EXTRA light groups after the second pivot (k_light plain only)
-    bool pivx_on = false;
+    bool pivx_on = false;      // pivx holds this run's extra pivots (k_light plain only)
     int pivx_kept = 0;  // extra pivots the pivot pass computed this run (PIV_EXTRA_PLAIN or PIV_EXTRA)
     int light_npx = 0;  // ... and how many k_light checks
-    DevBuf gdrow, dlist, dbits;  // dense light groups: group -> bitmap row, row -> group, the bitmaps
     u32* dbits_p = nullptr;      // the bitmaps in use (dbits)
-    DevBuf iflag, iexcl, iorder; // k_light's issue order (k_light_long_flags / k_light_order)
     hipStream_t side = nullptr;  // k_light_packed beside k_light (their slots are disjoint), joined before the compaction
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // early hand-over (rdf_set_handover): pinned host buffers the unpaged discovery fills on a copy stream while it still
@@ -145,15 +229,11 @@ struct rdf_ctx {
     bool hv_gpu_wait = false;
     bool dense_on = false;
     u64 dwords = 0, n_dense = 0;
-    int dense_div = -1;                   // RDFIND_DENSE (0: no bitmaps; -1: by input, d_dense_flags)
     bool dense_flagged = false;           // d_dense_flags numbered rows this run (d_dense_build fills them)
-    u64 dense_min = LIGHT_DENSE_MIN;      // RDFIND_DENSE_MIN (test hook: bitmaps for small groups too)
     bool sig_on = false;  // lsig holds this run's signatures (RDFIND_SIG=0 turns the filter off)
     bool sig_packed = false;  // the packed light path tests them too (RDFIND_SIG=1; default 2: k_light only)
     bool piv2_on = false;     // piv2 holds this run's second pivots
     bool piv2_packed = true;  // ... and the packed light path checks them first too (RDFIND_PIV2=2: k_light only)
-    DevBuf ctab, cflag, ccid, ckeys, ckeys_tmp, coff, cmask, cpiv, cnch, cchoff, ccnt, lwoff, clists, cself, cmcnt, cobase,
-        ctiles, ctoff;
     u64 n_class_members = 0, n_classes = 0, n_class_out = 0;
     // compact result: the class part (members x shared lists) is expanded into `out` only on demand
     bool class_pending = false;
@@ -164,19 +244,16 @@ struct rdf_ctx {
     u32 result_form = 0;
     u64 res_K = 0, res_nx = 0, res_wh = 0, res_h0 = 0;
     bool res_bits = false;
-    DevBuf hpos;
     // ... and their expansion into `out` (k_heavy_write) deferred to the first row accessor, like the class part:
     // work items [hp_h0, hp_h0 + hp_W) at output offset hp_K
     bool heavy_pending = false;
     u64 hp_W = 0, hp_h0 = 0, hp_K = 0;
-    DevBuf loff;  // list offsets of the shared (class) ref lists
     // paged discovery (rdf_discover_cinds_paged / rdf_next_page): dependents in ranges, one page at a time
     bool paged = false, pg_unary_done = false;
     u32 pg_flags = 0, pg_next = 0;
     u64 pg_budget = 0, pg_Eu = 0, pg_HC = 0, pg_NT = 0, pg_WM = 0, pg_pages = 0;
     std::vector<u64> h_choffl, h_choffh, h_eoffu;
     bool hclassed = false;  // binary heavy-only dependents emitted from class lists (single GPU, S2L semantics)
-    DevBuf pedges, pedges_tmp;
     u64 ncap = 0;
     u64 n_explicit_raw = 0, n_light_chunks = 0, n_light_survivors = 0, n_multi_items = 0;
     rdf_fc_stats fstats = {};
@@ -187,7 +264,6 @@ struct rdf_ctx {
     u32 rank = 0, nranks = 1;
     u32 sh_rank = 0, sh_nranks = 1, sh_ms = 1, sh_flags = 0;
     u64 sh_nfreq[3] = {0, 0, 0}, sh_nkeys = 0;
-    DevBuf wts, wtp, wto;  // sharded input: the triples received for this rank's join shard
     int sh_proj = 7, sh_phase = -1;
     u64 sh_WH = 0, sh_H = 0, sh_E = 0, sh_tcapc = 0;
     u32 h_hist_local[256] = {};
@@ -196,17 +272,7 @@ struct rdf_ctx {
     u64 x_count = 0, x_recv_count = 0;
     u32 x_bytes = 8;
     bool x_imported = true;
-    DevBuf item_dep, eblk, lslot, npk, pkoff, pk_dep, nmch, mchoff, mch_dep;
-    DevBuf uhist, urecs, usl, cntg, fstage, bfreq, boff, fbits, brkeys;  // partitioned K1 / K2 (counts.inl)
-    DevBuf xsend, xrecv, gbest, nrl, smask, smask_tmp, cpairs, cpairs_tmp, obounds;
-    DevBuf lmask, hrep, vpairs, vcoff, vpiv;  // holder-first light exchange (sh_phase5 / sh_phase15)
-    DevBuf ebown, segb, sege, seglen;         // this rank's binary dependents' final pairs; dependent segments
-    DevBuf bslots, bcounts;                   // light pass B's output slots (pass A's stay in epairs_tmp / lslot)
-    DevBuf ukeys, ukeys_tmp;                  // sharded: frequent unary keys (owned, then every rank's, sorted)
-    // sharded ingest (rdf_shard_parse_begin): local terms routed to their owners, the owner's dictionary, global ids
-    DevBuf ithv, ikeys, ikeys_tmp, iwords, iwoff, ihdr, ipay, ibnd, iwb, rhdr, rlen, rwords, rwoff, rts, rhv, rvalid, rtab,
-        rslot, rrep, rfirst, rfid, rhist, rreply, own_text, own_off, own_len, gmapv;
-    DevBuf dneed, dnpos, dwn, dwo, dhdr, dlen, dlwords, dwoff, tids, tlenv, toffv, tout;  // dictionary by owner lookup
+    // sharded ingest (rdf_shard_parse_begin)
     bool ingest_sharded = false;              // the resident ids are global ids of a sharded ingest
     u32 own_n = 0, own_base = 0;
     u64 ing_Vl = 0, ing_m = 0;
@@ -229,8 +295,7 @@ struct rdf_ctx {
     bool pend_heavy = false;
     bool spare_fc = false, spare_groups = false;  // reclaim_spare may release these stages' scratch
     bool spare_x = false;  // ... and the exchange buffers, from the routing of the triples to the end of the group build
-    DevBuf ecache;                   // join ranges: each range's scanned K3 block offsets from its first emission
-    std::vector<u64> ecache_je;      // ... and its record-slot count  // heavy threshold / count of the last group build still on the device (hist + 256, + 258)
+    std::vector<u64> ecache_je;      // join ranges: each range's record-slot count (its block offsets: ecache)  // heavy threshold / count of the last group build still on the device (hist + 256, + 258)
     // per kernel-family device timers (events on the context stream)
     static constexpr int kTSeg = 32;  // segments per timer (a kernel family may run in several places: the two light
                                       // passes record ~14 light segments)
@@ -241,6 +306,17 @@ struct rdf_ctx {
     u64 heavy_candidates = 0;
     u64 light_candidates = 0, light_entries = 0;  // pivot members / group entries of dependents with light groups
 };
+
+// f(buffer, its table entry) for every device buffer of the context
+template <typename F>
+static void for_each_buf(rdf_ctx* c, F f) {
+    for (const BufEntry& e : kBufs) f(c->*e.field, e);
+}
+static u64 class_bytes(rdf_ctx* c, BufClass cls) {
+    u64 t = 0;
+    for_each_buf(c, [&](DevBuf& b, const BufEntry& e) { t += e.cls == cls ? b.cap : 0; });
+    return t;
+}
 
 static void tbegin(rdf_ctx* c, int id) {
     if (c->tn[id] < rdf_ctx::kTSeg) (void)hipEventRecord(c->tev[2 * (id * rdf_ctx::kTSeg + c->tn[id])], c->stream);
@@ -287,19 +363,15 @@ static rdf_status fail(rdf_ctx* c, rdf_status code, const std::string& msg) {
 // every step cost seconds: c4 at 10^9 triples spent 4.3 of 6.4 s per step outside its kernels) and are released
 // only when an allocation of a later stage would otherwise fail.
 static bool reclaim_spare(rdf_ctx* c, const DevBuf* keep) {
-    const std::vector<DevBuf*> fc_scratch = {&c->brkeys, &c->brkeys2, &c->tkeys, &c->urecs};
-    const std::vector<DevBuf*> grp_scratch = {&c->rec, &c->rec_tmp, &c->fk, &c->fk_tmp, &c->rstore};
-    const std::vector<DevBuf*> x_scratch = {&c->xsend, &c->xrecv};
     bool any = false;
-    for (int k = 0; k < 3; ++k) {
-        if (!(k == 0 ? c->spare_fc : k == 1 ? c->spare_groups : c->spare_x)) continue;
-        for (DevBuf* b : (k == 0 ? fc_scratch : k == 1 ? grp_scratch : x_scratch)) {
-            if (b == keep || !b->p) continue;
-            if (!any) (void)hipStreamSynchronize(c->stream);  // queued kernels may still read them
-            b->release();
-            any = true;
-        }
-    }
+    for_each_buf(c, [&](DevBuf& b, const BufEntry& e) {
+        const bool spare = e.cls == BUF_SPARE_FC ? c->spare_fc : e.cls == BUF_SPARE_GROUPS ? c->spare_groups
+                                                                                             : e.cls == BUF_SPARE_X && c->spare_x;
+        if (!spare || &b == keep || !b.p) return;
+        if (!any) (void)hipStreamSynchronize(c->stream);  // queued kernels may still read them
+        b.release();
+        any = true;
+    });
     (void)hipGetLastError();
     return any;
 }
@@ -349,8 +421,7 @@ static u64 next_pow2(u64 x) {
 // instead of blocking in hipStreamSynchronize (measured: no gain on c2, 10.27 vs 10.23 ms, profiles/r04_sync_trace_*).
 // RDFIND_SYNC_TRACE=1: every wait prints "SYNC <line> <t_us> <wait_us>" to stderr (tools/sync_trace.py).
 static hipError_t stream_wait(hipStream_t s, int line) {
-    static const bool trace = getenv("RDFIND_SYNC_TRACE") != nullptr;
-    static const bool spin = getenv("RDFIND_SPIN") && atoi(getenv("RDFIND_SPIN")) != 0;
+    const bool trace = proc_switches().sync_trace, spin = proc_switches().spin;
     using clk = std::chrono::steady_clock;
     static const clk::time_point t00 = clk::now();
     const clk::time_point t0 = trace ? clk::now() : clk::time_point();
@@ -459,52 +530,24 @@ static inline unsigned vgrid(u64 blocks) { return (unsigned)std::min<u64>(std::m
 static inline u64 wave_blocks(u64 waves) { return (waves + RDF_WAVES_PER_BLOCK - 1) / RDF_WAVES_PER_BLOCK; }
 static inline u64 thread_blocks(u64 threads) { return (threads + RDF_BLOCK - 1) / RDF_BLOCK; }
 
-// every device buffer a context owns (release on destroy; rdf_device_bytes)
-static std::vector<DevBuf*> ctx_buffers(rdf_ctx* c) {
-    return {&c->scal, &c->ts, &c->tp, &c->to, &c->cnt, &c->tkeys, &c->tcnt, &c->bkeys, &c->bkeys_tmp,
-                      &c->lkeys, &c->lvals, &c->flags, &c->pos, &c->rec, &c->rec_tmp, &c->support, &c->fidx,
-                      &c->fcap, &c->frank, &c->fval, &c->fext, &c->info, &c->fk, &c->fk_tmp, &c->fpos, &c->cstart, &c->skip, &c->gflag, &c->gexcl, &c->goff,
-                      &c->gcap, &c->gmap, &c->csup,
-                      &c->doff, &c->dcur, &c->dgrp, &c->jhist, &c->rsup, &c->lsup, &c->hot, &c->hotc, &c->jrmap, &c->offp, &c->hist, &c->heavy_list, &c->hbit, &c->bcomp, &c->bkeyc,
-                      &c->pcnt, &c->poff, &c->pcur, &c->plist, &c->pivot, &c->nchl, &c->nchh, &c->choffl,
-                      &c->choffh, &c->epairs, &c->epairs_tmp, &c->eoff, &c->hcounts, &c->hoff, &c->hbits, &c->cbits, &c->hown, &c->cown, &c->sbase, &c->dcls, &c->crep, &c->out,
-                      &c->stage_rows, &c->nitl, &c->itoffl, &c->dead, &c->ebin,
-                      &c->pseg, &c->psegoff, &c->pbest, &c->pnl, &c->lsig, &c->brkeys2, &c->bstart2, &c->ginfo, &c->gsums, &c->piv2, &c->pivx, &c->ecache, &c->ctab, &c->cflag, &c->ccid, &c->ckeys,
-                      &c->ckeys_tmp, &c->coff, &c->cmask, &c->cpiv, &c->cnch, &c->cchoff, &c->ccnt, &c->lwoff,
-                      &c->clists, &c->cself, &c->cmcnt, &c->cobase, &c->ctiles, &c->ctoff, &c->pedges, &c->pedges_tmp,
-                      &c->item_dep, &c->eblk, &c->lslot, &c->npk, &c->pkoff, &c->pk_dep, &c->nmch, &c->mchoff, &c->mch_dep, &c->uhist, &c->urecs, &c->usl, &c->cntg, &c->fstage, &c->bfreq, &c->boff,
-                      &c->fbits, &c->brkeys, &c->xsend, &c->xrecv, &c->gbest, &c->nrl, &c->smask, &c->smask_tmp, &c->cpairs, &c->cpairs_tmp,
-                      &c->obounds, &c->lmask, &c->hrep, &c->vpairs, &c->vcoff, &c->vpiv, &c->runoff, &c->rundep, &c->dheap, &c->dtoff, &c->cslen, &c->csoff,
-                      &c->cstr, &c->flen, &c->floff, &c->fbuf, &c->drows, &c->ppart, &c->wts, &c->wtp,
-            &c->wto, &c->arcnt, &c->ar_bits, &c->ar_rules, &c->arref, &c->loff, &c->gdrow, &c->dlist, &c->dbits, &c->ebown, &c->bslots, &c->bcounts, &c->segb, &c->sege, &c->seglen, &c->ukeys,
-            &c->ukeys_tmp, &c->ithv, &c->ikeys, &c->ikeys_tmp, &c->iwords, &c->iwoff, &c->ihdr, &c->ipay, &c->ibnd, &c->iwb,
-            &c->rhdr, &c->rlen, &c->rwords, &c->rwoff, &c->rts, &c->rhv, &c->rvalid, &c->rtab, &c->rslot, &c->rrep, &c->rfirst,
-            &c->rfid, &c->rhist, &c->rreply, &c->own_text, &c->own_off, &c->own_len, &c->gmapv, &c->dneed, &c->dnpos, &c->dwn,
-            &c->dwo, &c->dhdr, &c->dlen, &c->dlwords, &c->dwoff, &c->tids, &c->tlenv, &c->toffv, &c->tout, &c->rstore, &c->jbh, &c->iflag, &c->iexcl, &c->iorder, &c->ukey, &c->utab, &c->urep, &c->ucnt, &c->unoff, &c->uebin, &c->umem, &c->hpos};
-}
-
-// RDFIND_MEM_REPORT=1: after each rdf_run, the context's buffers of >= 256 MiB (name, GiB) on stderr, largest first
-static const char* const kBufNames[] = {"scal", "ts", "tp", "to", "cnt", "tkeys", "tcnt", "bkeys", "bkeys_tmp", "lkeys", "lvals", "flags", "pos", "rec", "rec_tmp", "support", "fidx", "fcap", "frank", "fval", "fext", "info", "fk", "fk_tmp", "fpos", "cstart", "skip", "gflag", "gexcl", "goff", "gcap", "gmap", "csup", "doff", "dcur", "dgrp", "jhist", "rsup", "lsup", "hot", "hotc", "jrmap", "offp", "hist", "heavy_list", "hbit", "bcomp", "bkeyc", "pcnt", "poff", "pcur", "plist", "pivot", "nchl", "nchh", "choffl", "choffh", "epairs", "epairs_tmp", "eoff", "hcounts", "hoff", "hbits", "cbits", "hown", "cown", "sbase", "dcls", "crep", "out", "stage_rows", "nitl", "itoffl", "dead", "ebin", "pseg", "psegoff", "pbest", "pnl", "lsig", "brkeys2", "bstart2", "ginfo", "gsums", "piv2", "pivx", "ecache", "ctab", "cflag", "ccid", "ckeys", "ckeys_tmp", "coff", "cmask", "cpiv", "cnch", "cchoff", "ccnt", "lwoff", "clists", "cself", "cmcnt", "cobase", "ctiles", "ctoff", "pedges", "pedges_tmp", "item_dep", "eblk", "lslot", "npk", "pkoff", "pk_dep", "nmch", "mchoff", "mch_dep", "uhist", "urecs", "usl", "cntg", "fstage", "bfreq", "boff", "fbits", "brkeys", "xsend", "xrecv", "gbest", "nrl", "smask", "smask_tmp", "cpairs", "cpairs_tmp", "obounds", "lmask", "hrep", "vpairs", "vcoff", "vpiv", "runoff", "rundep", "dheap", "dtoff", "cslen", "csoff", "cstr", "flen", "floff", "fbuf", "drows", "ppart", "wts", "wtp", "wto", "arcnt", "ar_bits", "ar_rules", "arref", "loff", "gdrow", "dlist", "dbits", "ebown", "bslots", "bcounts", "segb", "sege", "seglen", "ukeys", "ukeys_tmp", "ithv", "ikeys", "ikeys_tmp", "iwords", "iwoff", "ihdr", "ipay", "ibnd", "iwb", "rhdr", "rlen", "rwords", "rwoff", "rts", "rhv", "rvalid", "rtab", "rslot", "rrep", "rfirst", "rfid", "rhist", "rreply", "own_text", "own_off", "own_len", "gmapv", "dneed", "dnpos", "dwn", "dwo", "dhdr", "dlen", "dlwords", "dwoff", "tids", "tlenv", "toffv", "tout", "rstore", "jbh", "iflag", "iexcl", "iorder", "ukey", "utab", "urep", "ucnt", "unoff", "uebin", "umem", "hpos"};
-static bool mem_report_on() {
-    static const bool on = getenv("RDFIND_MEM_REPORT") && atoi(getenv("RDFIND_MEM_REPORT")) != 0;
-    return on;
+// bytes of the context's device buffers, the workspace included
+static u64 held_bytes(rdf_ctx* c) {
+    u64 total = c->ws.bytes();
+    for_each_buf(c, [&](DevBuf& b, const BufEntry&) { total += b.cap; });
+    return total;
 }
 // the context's peak of buffer bytes (RDFIND_MEM_REPORT only: summed at every allocation that changes a buffer)
 static void mem_track(rdf_ctx* c) {
-    if (!mem_report_on()) return;
-    size_t total = c->ws.bytes();
-    for (DevBuf* b : ctx_buffers(c)) total += b->cap;
-    c->peak_bytes = std::max<u64>(c->peak_bytes, total);
+    if (proc_switches().mem_report) c->peak_bytes = std::max<u64>(c->peak_bytes, held_bytes(c));
 }
+// RDFIND_MEM_REPORT=1: after each rdf_run, the context's buffers of >= 256 MiB (name, GiB) on stderr, largest first
 static void mem_report(rdf_ctx* c) {
-    if (!mem_report_on()) return;
-    std::vector<DevBuf*> bufs = ctx_buffers(c);
+    if (!proc_switches().mem_report) return;
     std::vector<std::pair<size_t, const char*>> big;
-    size_t total = 0;
-    for (size_t i = 0; i < bufs.size(); ++i) {
-        total += bufs[i]->cap;
-        if (bufs[i]->cap >= (256ull << 20)) big.push_back({bufs[i]->cap, i < sizeof(kBufNames) / sizeof(kBufNames[0]) ? kBufNames[i] : "?"});
-    }
+    for_each_buf(c, [&](DevBuf& b, const BufEntry& e) {
+        if (b.cap >= (256ull << 20)) big.push_back({b.cap, e.name});
+    });
+    const size_t total = held_bytes(c) - c->ws.bytes();
     std::sort(big.begin(), big.end(), [](const std::pair<size_t, const char*>& x, const std::pair<size_t, const char*>& y) {
         return x.first > y.first;
     });
@@ -523,36 +566,7 @@ rdf_status rdf_ctx_create(int device, rdf_ctx** out) {
     *out = nullptr;
     rdf_ctx* c = new rdf_ctx();
     c->device = device;
-    // test hook: RDFIND_COUNT_PATHS=atomic selects the global-atomic unary counting kernel (the fallback of
-    // the partitioned K1 for |V| > 2^26 / 3), so the parity tests cover both paths
-    const char* paths = getenv("RDFIND_COUNT_PATHS");
-    c->force_global_counts = paths && !strcmp(paths, "atomic");
-    // test hook: RDFIND_HEAVY_MIN=<power of two> lowers the minimum heavy-group size (default 64), so small
-    // parity inputs exercise the bitmask / class / heavy-only paths
-    const char* hcl = getenv("RDFIND_HCLASS");
-    c->allow_hclass = !(hcl && !strcmp(hcl, "0"));
-    const char* hmin = getenv("RDFIND_HEAVY_MIN");
-    if (hmin && atoll(hmin) > 0) c->heavy_min = (u64)atoll(hmin);
-    // dense light-group bitmaps: RDFIND_DENSE=<divisor> (groups of >= C / divisor members; 0 = off) and the test hook
-    // RDFIND_DENSE_MIN=<members> (absolute minimum, default LIGHT_DENSE_MIN)
-    if (const char* dd = getenv("RDFIND_DENSE")) c->dense_div = atoi(dd);
-    // test hook: RDFIND_GROUP_RANGE=<records> builds the capture groups in join-value ranges of at most that many
-    // K3 records (the path inputs of >= 2^32 / 9 triples take), so small parity inputs run it
-    if (const char* gr = getenv("RDFIND_GROUP_RANGE"))
-        if (atoll(gr) > 0) c->group_range_records = (u64)atoll(gr);
-    if (const char* dm = getenv("RDFIND_DENSE_MIN"))
-        if (atoll(dm) > 0) c->dense_min = (u64)atoll(dm);
-    if (const char* hq = getenv("RDFIND_HOLDER_Q")) c->holder_qbits = std::max(0, std::min(atoi(hq), 8));
-    if (const char* tf = getenv("RDFIND_TEST_FAIL_LAUNCH")) c->test_fail_launch = tf;
-    if (const char* to = getenv("RDFIND_TEST_OOM_DISCOVERY")) c->test_oom_discovery = atoi(to) != 0;
-    if (const char* tf = getenv("RDFIND_TEST_FAIL_SHARD")) {
-        if (sscanf(tf, "%d:%d", &c->test_fail_rank, &c->test_fail_phase) != 2) c->test_fail_rank = c->test_fail_phase = -1;
-    }
-    if (const char* hb = getenv("RDFIND_HOT_BALANCE")) c->hot_balance = atoi(hb) != 0;
-    if (const char* rk = getenv("RDFIND_RANGE_KEEP")) c->range_keep = atoi(rk) != 0;
-    if (const char* ld = getenv("RDFIND_LIGHT_DEDUP")) c->light_dedup = atoi(ld) != 0 ? 1 : 0;
-    if (const char* dm = getenv("RDFIND_DUP_MIN")) c->dup_min = (u32)std::max(1, atoi(dm));
-    if (const char* um = getenv("RDFIND_U1_RADIX_MIN")) c->u1_radix_min = strtoull(um, nullptr, 10);
+    c->sw = read_switches();
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking);
@@ -581,7 +595,7 @@ void rdf_ctx_destroy(rdf_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->side) (void)hipStreamSynchronize(c->side);
     if (c->hstream) (void)hipStreamSynchronize(c->hstream);
-    for (DevBuf* b : ctx_buffers(c)) b->release();
+    for_each_buf(c, [](DevBuf& b, const BufEntry&) { b.release(); });
     c->ws.release();
     if (c->hscal) (void)hipHostFree(c->hscal);
     if (c->hread) (void)hipHostFree(c->hread);
@@ -589,10 +603,9 @@ void rdf_ctx_destroy(rdf_ctx* c) {
         if (e) (void)hipEventDestroy(e);
     for (auto& e : c->tev)
         if (e) (void)hipEventDestroy(e);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
+    for (hipEvent_t e : {c->ev_fork, c->ev_join, c->hv_ev, c->hv_done})
+        if (e) (void)hipEventDestroy(e);
     if (c->hstream) (void)hipStreamDestroy(c->hstream);
-    if (c->hv_ev) (void)hipEventDestroy(c->hv_ev);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -608,9 +621,7 @@ rdf_status rdf_sync(rdf_ctx* c) {
 
 rdf_status rdf_device_bytes(rdf_ctx* c, uint64_t* bytes) {
     if (!c || !bytes) return RDF_ERR_ARG;
-    u64 t = c->ws.bytes();
-    for (DevBuf* b : ctx_buffers(c)) t += b->cap;
-    *bytes = t;
+    *bytes = held_bytes(c);
     return RDF_OK;
 }
 
@@ -627,20 +638,13 @@ static rdf_status check_terms(rdf_ctx* c, u64 n, u32 num_terms) {
 // released first: a test sequence c4 at 0.4 (400M triples) -> c5 at 0.3 (3M triples, 10^10 CINDs) must not carry
 // the first run's buffers into the second run's growth.
 static void release_run_buffers(rdf_ctx* c, u64 n_next, bool always = false) {
-    const DevBuf* keep[] = {&c->scal, &c->ts, &c->tp, &c->to, &c->dheap, &c->dtoff, &c->own_text, &c->own_off, &c->own_len};
-    auto kept = [&](const DevBuf* b) {
-        for (const DevBuf* k : keep)
-            if (k == b) return true;
-        return false;
-    };
-    u64 held = c->ws.bytes();
-    for (DevBuf* b : ctx_buffers(c))
-        if (!kept(b)) held += b->cap;
+    const u64 held = held_bytes(c) - class_bytes(c, BUF_INPUT);
     if (!always && held <= std::max<u64>(4ull << 30, n_next << 10)) return;
     (void)hipStreamSynchronize(c->stream);
     c->paged = false;
-    for (DevBuf* b : ctx_buffers(c))
-        if (!kept(b)) b->release();
+    for_each_buf(c, [](DevBuf& b, const BufEntry& e) {
+        if (e.cls != BUF_INPUT) b.release();
+    });
     c->ws.release();
     c->dense_on = false;
     c->class_pending = false;
@@ -850,9 +854,9 @@ rdf_status rdf_parse_ntriples(rdf_ctx* c, const char* text, uint64_t nbytes, uin
     if (ms) HIP_TRY(c, hipEventElapsedTime(ms, c->ev[6], c->ev[7]));
     // parse-only scratch (~36 B per term occurrence + the slot table): only the text and the term table stay,
     // which rdf_set_dictionary_parsed needs, so discovery gets the HBM back
-    for (DevBuf* b : {&c->ncnt, &c->ncoff, &c->nlstart, &c->ntstart, &c->ntlen, &c->nvalid, &c->nlpos, &c->nhv,
-                      &c->nslot, &c->ntab, &c->nrep, &c->nfirst, &c->nfid})
-        b->release();
+    for_each_buf(c, [](DevBuf& b, const BufEntry& e) {
+        if (e.cls == BUF_PARSE) b.release();
+    });
     c->s = c->ts.as<u32>();
     c->p = c->tp.as<u32>();
     c->o = c->to.as<u32>();
@@ -900,7 +904,7 @@ static rdf_status fc_unary_part(rdf_ctx* c, const u32* s, const u32* p, const u3
     // keys live in K2's record buffers, which the next stage needs anyway.  c4 at 10^9 triples (22,891 buckets of 2^15
     // keys): K1 53.1 -> 42.9 ms; c4 at 0.4 (18,313 buckets, two blocks per CU) 14.1 -> 16.8 and c3 2.4 -> 4.6 lose, so
     // they keep the partition passes (profiles/r06_k1_radix_ab.log).  RDFIND_U1_RADIX_MIN=<3n> replaces the rule
-    const bool radix_rule = c->u1_radix_min ? 3 * n >= c->u1_radix_min : 3 * n >= U1_RADIX_MIN && NB * 4 > U1_RADIX_LDS;
+    const bool radix_rule = c->sw.u1_radix_min ? 3 * n >= c->sw.u1_radix_min : 3 * n >= U1_RADIX_MIN && NB * 4 > U1_RADIX_LDS;
     const bool radix = radix_rule && 3 * n < (1ull << 32) && K <= 0xffffffffull;
     const void* recs = nullptr;
     unsigned G = 1;
@@ -1009,7 +1013,7 @@ static rdf_status fc_unary(rdf_ctx* c, u64 nfreq[3]) {
     TRY(fc_unary_alloc(c));
     const int ubits = fc_ubits(K);
     const u64 NB = (K + (1ull << ubits) - 1) >> ubits;
-    if (n && NB <= U2_MAXB && !c->force_global_counts) {
+    if (n && NB <= U2_MAXB && !c->sw.count_atomic) {
         TRY(fc_unary_part(c, c->s, c->p, c->o, n, ubits, NB, false));
         return fc_unary_finish(c, nfreq);
     }
@@ -1102,11 +1106,9 @@ static rdf_status fc_binary_part(rdf_ctx* c, const u32* s, const u32* p, const u
     ENSURE(c, pos, maxrec * 4);    // spill list: counts
     const u64 bmax = maxrec / std::max<u32>(c->ms, 1) + 1;  // frequent keys: each counts >= ms of <= 3n records
     ENSURE(c, bkeys, bmax * 8);
-    static const int split_mode = getenv("RDFIND_B2_SPLIT") ? atoi(getenv("RDFIND_B2_SPLIT")) : 1;
+    const int split_mode = c->sw.b2_split;
     // large inputs: compact records grouped by hash prefix with the radix passes (k_b2_emit, radix_partition_hashed)
-    static const u64 radix_min = getenv("RDFIND_B2_RADIX_MIN") ? strtoull(getenv("RDFIND_B2_RADIX_MIN"), nullptr, 10)
-                                                               : B2_RADIX_MIN;
-    if (split_mode != 0 && 3 * n >= radix_min && maxrec < (1ull << 32)) {
+    if (split_mode != 0 && 3 * n >= c->sw.b2_radix_min && maxrec < (1ull << 32)) {
         ENSURE(c, brkeys2, maxrec * 8);
         HIP_TRY(c, hipMemsetAsync(dscal(c, 2), 0, 8, st));
         hipLaunchKernelGGL(k_b2_emit, dim3(grid_for(n, RDF_BLOCK * PART_U, kGrid)), dim3(RDF_BLOCK), 0, st, s, p, o, n, V,
@@ -1155,7 +1157,7 @@ static rdf_status fc_binary_part(rdf_ctx* c, const u32* s, const u32* p, const u
         ENSURE(c, brkeys2, maxrec * 8);
         ENSURE(c, bstart2, ((u64)NBc + 1) * 4);
         // RDFIND_TEST_FAIL_LAUNCH=k_b2_split (test hook): launched with an invalid block size, so the launch fails
-        const unsigned sblock = c->test_fail_launch == "k_b2_split" ? 4 * 1024 : RDF_BLOCK;
+        const unsigned sblock = c->sw.test_fail_launch == "k_b2_split" ? 4 * 1024 : RDF_BLOCK;
         hipLaunchKernelGGL(k_b2_split, dim3(std::min<u32>(NB2, B2_SPLIT_GRID)), dim3(sblock), 0, st, c->brkeys.as<u64>(),
                            c->uhist.as<u32>(), NB2, G2, bits, sub, c->brkeys2.as<u64>(), c->bstart2.as<u32>());
         // bstart2 (the sub-bucket starts) is consumed as record offsets by k_b2_slices and k_b2_count: a launch that
@@ -1327,7 +1329,7 @@ rdf_status rdf_frequent_conditions(rdf_ctx* c, uint32_t min_support, rdf_fc_stat
     tend(c, RDF_T_UNARY);
     tbegin(c, RDF_T_BINARY);
     u64 B = 0, nkeys = 0, S = 0;
-    if (c->n && !c->force_global_counts) TRY(fc_binary_part(c, c->s, c->p, c->o, c->n, false, &B, &nkeys, &S));
+    if (c->n && !c->sw.count_atomic) TRY(fc_binary_part(c, c->s, c->p, c->o, c->n, false, &B, &nkeys, &S));
     else if (c->n) TRY(fc_binary_global(c, &B, &nkeys));
     TRY(fc_binary_index(c, B));
     tend(c, RDF_T_BINARY);
@@ -1540,8 +1542,7 @@ static rdf_status g_emit_range(rdf_ctx* c, int proj, JoinSel js, u64 cap_rec, u3
     // into its own region of rec_tmp (9 x per slots), then k_emit_compact packs the regions into rec by the scanned
     // block counts; no padding reaches the sort.  c2 emit 0.86 -> 0.73 ms, sort 1.79 -> 1.71, c3 step 72.4 -> 69.9 ms
     // (profiles/r05_emit_onepass_ab.log).  RDFIND_EMIT_ONEPASS=0: the count pass + write pass with padding
-    static const bool onepass_env = !getenv("RDFIND_EMIT_ONEPASS") || atoi(getenv("RDFIND_EMIT_ONEPASS")) != 0;
-    const bool onepass = onepass_env && cache == 0 && slot_cap >= 9 * n;
+    const bool onepass = c->sw.emit_onepass && cache == 0 && slot_cap >= 9 * n;
     if (onepass && n) {
         u64* eoff = c->eblk.as<u64>() + (eg + 1ull);
         HIP_TRY(c, hipMemsetAsync(c->eblk.as<u64>() + eg, 0, 8, st));  // records emitted, repeats included
@@ -1812,7 +1813,7 @@ static rdf_status g_compact_groups(rdf_ctx* c) {
 static rdf_status g_range_keep_plan(rdf_ctx* c) {
     const std::vector<rdf_ctx::JoinRange>& ranges = c->jranges;
     c->jr_keep = false;
-    if (!c->range_keep || ranges.empty() || ranges.size() > EMIT_MAX_RANGES) return RDF_OK;
+    if (!c->sw.range_keep || ranges.empty() || ranges.size() > EMIT_MAX_RANGES) return RDF_OK;
     u64 total = 0;
     c->jr_seg.assign(ranges.size() + 1, 0);
     c->jr_J.assign(ranges.size(), 0);
@@ -1823,10 +1824,11 @@ static rdf_status g_range_keep_plan(rdf_ctx* c) {
     c->jr_seg[ranges.size()] = total;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return RDF_OK;
-    // held by this context and reusable here: the spare stages' scratch and the range buffers of an earlier build
-    const u64 held = (u64)c->brkeys.cap + c->brkeys2.cap + c->tkeys.cap + c->urecs.cap +
-                     (c->spare_x ? (u64)c->xsend.cap + c->xrecv.cap : 0ull) + c->rec.cap + c->rec_tmp.cap + c->fk.cap +
-                     c->fk_tmp.cap + c->rstore.cap;
+    // held by this context and reusable here: the spare stages' scratch and the range buffers of an earlier build.
+    // spare_fc holds (fc_end set it, single GPU and sharded); spare_groups does not (g_record_bits cleared it), but the
+    // group buffers are this build's own, which it is about to size; spare_x holds in a sharded build only
+    const u64 held = class_bytes(c, BUF_SPARE_FC) + class_bytes(c, BUF_SPARE_GROUPS) +
+                     (c->spare_x ? class_bytes(c, BUF_SPARE_X) : 0);
     const u64 global = 8 * 9 * c->n / 2 + 16ull * (c->V ? c->V : 1) + (4ull << 30);
     const u64 need = 8 * total + 40 * c->jr_cap_rec + global;  // rec_tmp (8 B per record) is not used when keeping
     if ((u64)free_b + held < need) {
@@ -2134,8 +2136,7 @@ static u64 auto_range_records(rdf_ctx* c) {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 1ull << 30;
     // spare buffers an allocation of the build may release (reclaim_spare)
-    const u64 held = (u64)c->brkeys.cap + c->brkeys2.cap + c->tkeys.cap + c->urecs.cap +
-                     (c->spare_x ? (u64)c->xsend.cap + c->xrecv.cap : 0ull) + c->rstore.cap;
+    const u64 held = class_bytes(c, BUF_SPARE_FC) + (c->spare_x ? class_bytes(c, BUF_SPARE_X) : 0) + c->rstore.cap;
     const u64 avail = (u64)free_b + held;
     // ~4.5 records per triple kept
     const u64 global = 8 * 9 * c->n / 2 + 16ull * (c->V ? c->V : 1) + (4ull << 30);
@@ -2162,8 +2163,8 @@ static rdf_status g_size_hist(rdf_ctx* c, u32* h_hist) {
 
 // heavy threshold from the (global) histogram; 0 = no heavy groups
 static u64 heavy_threshold(const rdf_ctx* c, const u32* hist) {
-    int tb = heavy_threshold_from_hist(hist, c->heavy_min);
-    return tb >= 0 ? std::max<u64>(bucket_min_size(tb), c->heavy_min) : 0;
+    int tb = heavy_threshold_from_hist(hist, c->sw.heavy_min);
+    return tb >= 0 ? std::max<u64>(bucket_min_size(tb), c->sw.heavy_min) : 0;
 }
 
 // groups of a histogram at or above the threshold (exact: a power-of-two heavy_min starts a bucket)
@@ -2189,7 +2190,7 @@ static rdf_status g_heavy_binary(rdf_ctx* c, u64 thr, u32 base, bool dev_thr = f
     u32* d_nheavy = c->hist.as<u32>() + 256;
     u64* d_thr = reinterpret_cast<u64*>(c->hist.as<u32>() + 258);
     HIP_TRY(c, hipMemsetAsync(d_nheavy, 0, 4, st));
-    if (dev_thr) hipLaunchKernelGGL(k_heavy_threshold, dim3(1), dim3(1), 0, st, c->hist.as<u32>(), c->heavy_min, d_thr);
+    if (dev_thr) hipLaunchKernelGGL(k_heavy_threshold, dim3(1), dim3(1), 0, st, c->hist.as<u32>(), c->sw.heavy_min, d_thr);
     if (G)
         hipLaunchKernelGGL(k_heavy_select, dim3(grid_for(G, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->goff.as<u64>(), G,
                            thr, dev_thr ? d_thr : nullptr, base, d_nheavy, c->heavy_list.as<u32>(), c->hbit.as<uint8_t>());
@@ -2284,8 +2285,8 @@ rdf_status rdf_build_capture_groups(rdf_ctx* c, const char* projection, rdf_grou
     c->nranks = 1;
     c->paged = false;
     c->n_group_ranges = 1;
-    if (c->group_range_records || 9 * c->n >= (1ull << 32)) {
-        TRY(g_build_ranges(c, proj, c->group_range_records ? c->group_range_records : auto_range_records(c)));
+    if (c->sw.group_range_records || 9 * c->n >= (1ull << 32)) {
+        TRY(g_build_ranges(c, proj, c->sw.group_range_records ? c->sw.group_range_records : auto_range_records(c)));
     } else {
         TRY(g_emit_sort_support(c, proj));
         TRY(g_compact_groups(c));
@@ -2332,8 +2333,7 @@ static CindView make_view(rdf_ctx* c, uint32_t flags) {
     v.dwords = c->dwords;
     v.prefilter = 0;
     v.p2done = 0;
-    static const int sweep_f = getenv("RDFIND_SWEEP_F") ? atoi(getenv("RDFIND_SWEEP_F")) : LIGHT_SWEEP_F;
-    v.sweep_f = sweep_f;
+    v.sweep_f = c->sw.sweep_f;
     return v;
 }
 
@@ -2347,11 +2347,11 @@ static rdf_status d_dense_flags(rdf_ctx* c) {
     const u64 G = c->G, C = c->C;
     c->dense_on = false;
     c->dense_flagged = false;
-    const int div = c->dense_div >= 0 ? c->dense_div : DENSE_DIV_STAGE;  // RDFIND_DENSE: one divisor for every input
+    const int div = c->sw.dense_div >= 0 ? c->sw.dense_div : DENSE_DIV_STAGE;  // RDFIND_DENSE: one divisor for every input
     if (div <= 0 || !G || !C) return RDF_OK;
-    auto clampd = [&](u64 m) { return (u32)std::min<u64>(std::max<u64>(m, c->dense_min), 0x7fffffffu); };
+    auto clampd = [&](u64 m) { return (u32)std::min<u64>(std::max<u64>(m, c->sw.dense_min), 0x7fffffffu); };
     const u32 dmin_stage = clampd((C + div - 1) / div);
-    const u32 dmin_other = c->dense_div >= 0 ? dmin_stage : clampd(std::min<u64>((C + 31) / 32, DENSE_MIN_ABS));
+    const u32 dmin_other = c->sw.dense_div >= 0 ? dmin_stage : clampd(std::min<u64>((C + 31) / 32, DENSE_MIN_ABS));
     tbegin(c, RDF_T_LIGHT);
     ENSURE(c, gflag, G * 4);
     ENSURE(c, gexcl, (G + 1) * 4);
@@ -2371,12 +2371,12 @@ static rdf_status d_dense_build(rdf_ctx* c, CindView& v, u64 nrows) {
     if (!c->dense_flagged || !nrows) return RDF_OK;
     const u64 G = c->G, C = c->C;
     const u64 dwords = ((C + 31) / 32 + 31) & ~31ull;  // rows start on 128-B lines
-    u64 budget = getenv("RDFIND_DENSE_BYTES") ? (u64)atoll(getenv("RDFIND_DENSE_BYTES")) : DENSE_BYTES;
+    u64 budget = c->sw.dense_bytes;
     size_t hfree = 0, htotal = 0;
     if (hipMemGetInfo(&hfree, &htotal) == hipSuccess) budget = std::min<u64>(budget, std::max<u64>(c->dbits.cap, hfree / 2));
     (void)hipGetLastError();
     const u64 rows = std::min<u64>(nrows, budget / (dwords * 4));
-    if (getenv("RDFIND_DEBUG_LIGHT"))
+    if (c->sw.debug_light)
         fprintf(stderr, "dense: C %llu G %llu rows %llu of %llu, %.1f MB\n", (unsigned long long)C, (unsigned long long)G,
                 (unsigned long long)rows, (unsigned long long)nrows, rows * dwords * 4 / 1e6);
     if (!rows) return RDF_OK;
@@ -2424,7 +2424,7 @@ static rdf_status d_pivot_local(rdf_ctx* c, CindView& v) {
     ENSURE(c, pnl, std::max<u64>(C, 1) * 4);
     // signature test in k_light only by default (mode 2): on the packed path (few groups per dependent) the extra
     // line per candidate cost more than it saved (c5 at 0.1: 20.8 vs 17.6 ms light); mode 1 tests it in both
-    static const int sig_mode = getenv("RDFIND_SIG") ? atoi(getenv("RDFIND_SIG")) : 2;
+    const int sig_mode = c->sw.sig;
     const bool sig_enabled = sig_mode != 0;
     c->sig_on = sig_enabled;
     c->sig_packed = sig_mode != 2;
@@ -2448,7 +2448,7 @@ static rdf_status d_pivot_local(rdf_ctx* c, CindView& v) {
     }
     tend(c, RDF_T_PIVOT);
     TRY(d_dense_flags(c));
-    static const int piv2_mode = getenv("RDFIND_PIV2") ? atoi(getenv("RDFIND_PIV2")) : 1;  // 2: k_light only
+    const int piv2_mode = c->sw.piv2;  // 2: k_light only
     const bool piv2_enabled = piv2_mode != 0;
     c->piv2_packed = piv2_mode != 2;
     u32* piv2 = nullptr;
@@ -2457,7 +2457,7 @@ static rdf_status d_pivot_local(rdf_ctx* c, CindView& v) {
         piv2 = c->piv2.as<u32>();
     }
     c->piv2_on = piv2_enabled;
-    static const bool pivx_enabled = piv2_enabled && (!getenv("RDFIND_PIVX") || atoi(getenv("RDFIND_PIVX")) != 0);
+    const bool pivx_enabled = piv2_enabled && c->sw.pivx;  // the extra pivots follow the second one
     u32* pivx = nullptr;
     if (pivx_enabled) {
         ENSURE(c, pivx, std::max<u64>(C, 1) * 4 * PIV_EXTRA);
@@ -2491,8 +2491,7 @@ static rdf_status d_pivot_local(rdf_ctx* c, CindView& v) {
         // member-weighted mean light group size sum(n^2) / sum(n): small groups -> the LDS-staging light variant
         c->light_stage = r[2] <= (u64)LIGHT_STAGE_AVG * r[1];
         c->light_wmean = r[1] ? r[2] / r[1] : 0;
-        static const char* force = getenv("RDFIND_STAGE");  // A/B and test hook: 0 / 1 forces the variant
-        if (force) c->light_stage = atoi(force) != 0;
+        if (c->sw.stage.set) c->light_stage = c->sw.stage.v != 0;  // RDFIND_STAGE forces the variant
     }
     // extra pivots: all PIV_EXTRA where the high-occupancy light variant may run (large groups), one elsewhere
     c->pivx_kept = !pivx ? 0
@@ -2540,12 +2539,10 @@ static rdf_status d_chunks(rdf_ctx* c, u64* WL, u64* WH, u64* WI, u64* WP) {
     c->n_multi_items = v[7];
     *WL = v[0];
     c->light_hiocc = !c->light_stage && c->light_wmean >= LIGHT_HIOCC_AVG && v[0] >= LIGHT_HIOCC_OCT * (u64)C;
-    static const char* hi = getenv("RDFIND_LIGHT_HIOCC");  // A/B and test hook: 0 / 1 forces the occupancy
-    if (hi) c->light_hiocc = !c->light_stage && atoi(hi) != 0;
+    if (c->sw.light_hiocc.set) c->light_hiocc = !c->light_stage && c->sw.light_hiocc.v != 0;  // RDFIND_LIGHT_HIOCC
     c->light_npx = std::min(c->pivx_kept, c->light_hiocc ? PIV_EXTRA : PIV_EXTRA_PLAIN);
-    static const char* npx = getenv("RDFIND_PIVX_N");  // A/B and test hook: how many extra pivots k_light checks
-    if (npx) c->light_npx = std::min(c->pivx_kept, atoi(npx));
-    if (getenv("RDFIND_DEBUG_LIGHT"))
+    if (c->sw.pivx_n.set) c->light_npx = std::min(c->pivx_kept, c->sw.pivx_n.v);  // RDFIND_PIVX_N
+    if (c->sw.debug_light)
         fprintf(stderr, "LIGHT weighted mean light group %llu, octets per capture %.1f (stage %d, hiocc %d, extra pivots %d of %d)\n",
                 (unsigned long long)c->light_wmean, C ? (double)v[0] / C : 0.0, (int)c->light_stage, (int)c->light_hiocc,
                 c->light_npx, c->pivx_kept);
@@ -2619,7 +2616,7 @@ static rdf_status d_light_kernels(rdf_ctx* c, const CindView& v, const u32* pivo
     HIP_TRY(c, hipMemsetAsync(counts.p, 0, nslot * 4, st));
 #ifdef RDF_LIGHT_STATS
     u32* lrec = nullptr;
-    if (WI && getenv("RDFIND_LIGHT_DUMP")) {
+    if (WI && c->sw.light_dump.set) {
         HIP_TRY(c, hipMalloc(&lrec, r.i1 * 96));
         HIP_TRY(c, hipMemset(lrec, 0, r.i1 * 96));
         HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(g_item_rec), &lrec, sizeof(lrec)));
@@ -2631,14 +2628,12 @@ static rdf_status d_light_kernels(rdf_ctx* c, const CindView& v, const u32* pivo
     if (!c->piv2_packed) vp.piv2 = nullptr;
     // the packed path checks the first extra pivot after the second one on large-group inputs (c3 full: packed + plain
     // light 27.5 -> 26.8 ms; c2, c5 lose 1-2 %: profiles/r04_light_ab_pivx_packed.log).  RDFIND_PIVX_PACKED=0/1 forces
-    static const char* pxp = getenv("RDFIND_PIVX_PACKED");
-    const bool pivx_packed = pxp ? atoi(pxp) != 0 : !c->light_stage && c->light_wmean >= PIVX_WMEAN;
+    const bool pivx_packed = c->sw.pivx_packed.set ? c->sw.pivx_packed.v != 0 : !c->light_stage && c->light_wmean >= PIVX_WMEAN;
     vp.npx = pivx_packed && c->pivx_kept ? 1 : 0;
     if (!vp.npx) vp.pivx = nullptr;
     // the packed dependents on the side stream, beside k_light (disjoint output octets): their blocks fill the SIMDs
     // k_light's long items leave idle (RDFIND_LIGHT_SIDE=0: one stream)
-    static const bool side_ok = !(getenv("RDFIND_LIGHT_SIDE") && atoi(getenv("RDFIND_LIGHT_SIDE")) == 0);
-    const bool side = side_ok && WP && WI;
+    const bool side = c->sw.light_side && WP && WI;
     if (side) {
         HIP_TRY(c, hipEventRecord(c->ev_fork, st));
         HIP_TRY(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
@@ -2657,8 +2652,7 @@ static rdf_status d_light_kernels(rdf_ctx* c, const CindView& v, const u32* pivo
         // little (c3 17.0 -> 17.2, c4 at 0.4 60.4 -> 61.1; profiles/r05_light_order_ab.log).  The partition is stable:
         // an octave-class order whose slots came from atomics measured 2.23 ms on c2 (consecutive items of one
         // dependent share its groups in L2; profiles/r05_light_order_classes_ab.log)
-        static const char* oenv = getenv("RDFIND_LIGHT_ORDER");
-        const u64 order_thr = oenv ? strtoull(oenv, nullptr, 10) : c->light_stage ? LIGHT_ORDER_MIN : 0;
+        const u64 order_thr = c->sw.light_order.set ? c->sw.light_order.v : c->light_stage ? LIGHT_ORDER_MIN : 0;
         const u32* order = nullptr;
         if (order_thr && WI < (1ull << 32)) {
             ENSURE(c, iflag, WI * 4);
@@ -2685,7 +2679,7 @@ static rdf_status d_light_kernels(rdf_ctx* c, const CindView& v, const u32* pivo
     if (lrec) {  // per-item records -> $RDFIND_LIGHT_DUMP (raw u32 x 24 per item)
         std::vector<u32> h(r.i1 * 24);
         HIP_TRY(c, ctx_copy(c, h.data(), lrec, r.i1 * 96, hipMemcpyDeviceToHost));
-        if (FILE* f = fopen(getenv("RDFIND_LIGHT_DUMP"), "wb")) {
+        if (FILE* f = fopen(c->sw.light_dump.v.c_str(), "wb")) {
             fwrite(h.data(), 96, r.i1, f);
             fclose(f);
         }
@@ -2754,9 +2748,8 @@ static rdf_status d_multi_items(rdf_ctx* c) {
 // c4 at 0.4 181.8 / 197.9, c4 at 0.05 11.2 / 12.5, c3 at 0.5 10.6 / 10.9, c5 at 0.1 17.9 / 20.4, c2 2.60 / 2.92), so the
 // two passes only run on request (RDFIND_LIGHT2=1, which the parity tests use) or with the sweeps off.
 static bool use_two_pass(const rdf_ctx* c, u64 WI) {
-    static const char* force = getenv("RDFIND_LIGHT2");
     if (!WI) return false;
-    if (force) return atoi(force) != 0;
+    if (c->sw.light2.set) return c->sw.light2.v != 0;
     return LIGHT_SWEEP_F == 0 && c->n_multi_items >= LIGHT2_MIN_ITEMS;
 }
 
@@ -3160,7 +3153,7 @@ static rdf_status d_light_dedup(rdf_ctx* c, const CindView& v) {
     // classes to pay for finding them (c2: 22 % of the light group entries, light 2.02 -> 1.80 ms, step -0.08 ms; c3
     // and c4 at 0.4: ~2.5 %, no gain; profiles/r06_light_dedup_ab.log).  The member count waits in scalar slot 9
     // (which no light-pass stage uses) until d_dedup_expand reads it with the pair count
-    const bool on = c->light_dedup < 0 ? c->light_stage : c->light_dedup != 0;
+    const bool on = c->sw.light_dedup < 0 ? c->light_stage : c->sw.light_dedup != 0;
     if (!on || v.literal || v.ar || c->nranks != 1 || !C) return RDF_OK;
     hipStream_t st = c->stream;
     const u64 tcap = next_pow2(2ull * C + 16);
@@ -3172,7 +3165,7 @@ static rdf_status d_light_dedup(rdf_ctx* c, const CindView& v) {
     HIP_TRY(c, hipMemsetAsync(dscal(c, 9), 0, 8, st));
     const dim3 g(grid_for(C, RDF_BLOCK, kGrid));
     hipLaunchKernelGGL(k_dup_insert, g, dim3(RDF_BLOCK), 0, st, v, c->nchl.as<u32>(), c->ukey.as<u64>(), c->utab.as<u64>(),
-                       tcap - 1, (u64)c->dup_min);
+                       tcap - 1, (u64)c->sw.dup_min);
     ENSURE(c, ucnt, (u64)C * 4);
     ENSURE(c, unoff, (C + 1ull) * 8);
     ENSURE(c, eoff, (C + 1ull) * 8);  // (scratch here: the members' chunk offsets; the explicit index rewrites it)
@@ -3254,7 +3247,7 @@ rdf_status rdf_discover_cinds(rdf_ctx* c, uint32_t flags, rdf_cind_stats* stats)
     c->paged = false;
     // test hook (RDFIND_TEST_OOM_DISCOVERY=1): the unpaged discovery reports RDF_ERR_OOM at once, so a caller's
     // fallback to pages runs on small inputs
-    if (c->test_oom_discovery) return fail(c, RDF_ERR_OOM, "test hook: the unpaged discovery runs out of memory");
+    if (c->sw.test_oom_discovery) return fail(c, RDF_ERR_OOM, "test hook: the unpaged discovery runs out of memory");
     hipStream_t st = c->stream;
     if (c->hv_capid && c->hv_sup && c->C && (u64)c->C <= c->hv_cap_cap) {  // the capture table is final: early copy
         HIP_TRY(c, hipEventRecord(c->hv_ev, st));
@@ -3286,7 +3279,7 @@ rdf_status rdf_discover_cinds(rdf_ctx* c, uint32_t flags, rdf_cind_stats* stats)
     else TRY(d_light(c, v, WI, WL, WP, &E, c->pivot.as<u32>()));
     bool indexed = false;
     TRY(d_dedup_expand(c, v, &E, &indexed));
-    if (getenv("RDFIND_LIGHT2_LOG"))
+    if (c->sw.light2_log)
         fprintf(stderr, "LIGHT2 two=%d items=%llu multi_chunk_items=%llu survivors=%llu explicit=%llu\n",
                 (int)two, (unsigned long long)WI, (unsigned long long)c->n_multi_items,
                 (unsigned long long)c->n_light_survivors, (unsigned long long)E);
@@ -3323,7 +3316,7 @@ rdf_status rdf_discover_cinds(rdf_ctx* c, uint32_t flags, rdf_cind_stats* stats)
         c->hv_pending = true;
     }
     // strategy 0's quirk filter is per dependent: keep the pivot scan there (RDFIND_HCLASS=0: test hook)
-    c->hclassed = !v.literal && c->allow_hclass && !v.ar;
+    c->hclassed = !v.literal && c->sw.allow_hclass && !v.ar;
     TRY(d_classes_single(c, v, &HC, &NT));
     if (c->hclassed) TRY(d_class_bin(c, v, &WH));
     TRY(d_heavy_count(c, v, WH, &H));
@@ -3530,7 +3523,7 @@ rdf_status rdf_discover_cinds_paged(rdf_ctx* c, uint32_t flags, uint64_t page_by
     c->h_eoffu.resize(c->Cu + 1ull);  // on the context stream: hipMemcpy would not wait for k_pair_offsets there
     HIP_TRY(c, hipMemcpyAsync(c->h_eoffu.data(), c->eoff.p, (c->Cu + 1ull) * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    c->hclassed = !v.literal && c->allow_hclass && !v.ar;
+    c->hclassed = !v.literal && c->sw.allow_hclass && !v.ar;
     TRY(d_classes_single(c, v, &HC, &NT));
     if (c->hclassed) TRY(d_class_bin(c, v, &WH));
     HIP_TRY(c, ctx_copy(c, c->h_choffh.data(), c->choffh.p, (c->C + 1ull) * 8, hipMemcpyDeviceToHost));
@@ -3673,7 +3666,7 @@ static rdf_status sh_phase10(rdf_ctx* c, rdf_exchange* req) {
     const int ubits = fc_ubits(K);
     const u64 NB = (K + (1ull << ubits) - 1) >> ubits;
     tbegin(c, RDF_T_UNARY);
-    if (n && NB <= U2_MAXB && !c->force_global_counts) {
+    if (n && NB <= U2_MAXB && !c->sw.count_atomic) {
         TRY(fc_unary_part(c, s, p, o, n, ubits, NB, true));
     } else {
         HIP_TRY(c, hipMemsetAsync(c->cntg.p, 0, K * 4, st));
@@ -3717,7 +3710,7 @@ static rdf_status sh_phase16(rdf_ctx* c, rdf_exchange* req) {
     c->hot_mask = 0;
     // (hot balancing packs a key as key << 32 | count with 0xffffffff as the slice-size marker: dictionaries whose 3V
     // keys reach it keep the hash owners)
-    if (!c->hot_balance || c->sh_nranks <= 1 || 3ull * (c->V ? c->V : 1) >= 0xffffffffull) {
+    if (!c->sw.hot_balance || c->sh_nranks <= 1 || 3ull * (c->V ? c->V : 1) >= 0xffffffffull) {
         HIP_TRY(c, hipStreamSynchronize(st));
         return x_request(c, req, RDF_X_ALLGATHERV_U64, c->ukeys.p, Bu, 11);
     }
@@ -3979,12 +3972,12 @@ static rdf_status sh_phase14(rdf_ctx* c, rdf_exchange* req) {
     c->sh_m = m;
     // a join shard whose K3 records exceed one sort's u32 offsets (>= 2^32/9 received triples, e.g. c4 at 10^9 triples
     // over 2 or 4 ranks) builds its groups in join ranges, as one GPU does: pass 1 here, pass 2 after the all-reduce
-    c->sh_ranged = c->group_range_records || 9 * m >= (1ull << 32);
+    c->sh_ranged = c->sw.group_range_records || 9 * m >= (1ull << 32);
     c->n_group_ranges = 1;
     {
         ReceivedTriples rt(c);  // K3 reads the received triples; the resident input stays this rank's slice
         if (c->sh_ranged) {
-            TRY(g_ranges_supports(c, c->sh_proj, c->group_range_records ? c->group_range_records : auto_range_records(c),
+            TRY(g_ranges_supports(c, c->sh_proj, c->sw.group_range_records ? c->sw.group_range_records : auto_range_records(c),
                                   shard_sel(c)));
             // this rank's supports, kept for pass 2 (the all-reduce brings the global ones)
             ENSURE(c, lsup, std::max<u64>(c->ncap, 1) * 4);
@@ -4050,7 +4043,7 @@ static rdf_status sh_phase3(rdf_ctx* c, rdf_exchange* req) {
     ENSURE(c, xsend, std::max<u64>(c->C, 1) * 8);
     if (c->C)
         hipLaunchKernelGGL(k_shard_best_keys, dim3(grid_for(c->C, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, c->stream,
-                           c->pbest.as<u64>(), c->info.as<CapInfo>(), c->C, c->rank, c->holder_qbits, c->xsend.as<u64>());
+                           c->pbest.as<u64>(), c->info.as<CapInfo>(), c->C, c->rank, c->sw.holder_qbits, c->xsend.as<u64>());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return x_request(c, req, RDF_X_ALLREDUCE_MIN_U64, c->xsend.p, c->C, 4);
 }
@@ -4770,7 +4763,7 @@ rdf_status rdf_shard_step(rdf_ctx* c, rdf_exchange* req) {
     if (!sh_phase_valid(c->sh_phase, false)) return fail(c, RDF_ERR_STATE, "rdf_shard_begin must be called first");
     if (!c->x_imported) return fail(c, RDF_ERR_STATE, "rdf_shard_import must supply the pending exchange first");
     HIP_TRY(c, hipSetDevice(c->device));
-    if ((int)c->sh_rank == c->test_fail_rank && c->sh_phase == c->test_fail_phase)
+    if ((int)c->sh_rank == c->sw.test_fail_shard.rank && c->sh_phase == c->sw.test_fail_shard.phase)
         return fail(c, RDF_ERR_OOM, "RDFIND_TEST_FAIL_SHARD: this rank fails at phase " + std::to_string(c->sh_phase));
     rdf_status r = RDF_OK;
     switch (c->sh_phase) {

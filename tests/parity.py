@@ -8,7 +8,7 @@
 * ``assert_rows_equal(ctx, d, ...)``: exact row-by-row parity of the current result with the materializing oracle, as
   sorted packed (dep, ref) keys + supports (vectorized; a Python set of 10^7 tuples took ~40 s per check);
 * ``dataset_npz(cfg, scale)``: the same input saved once as .npy files, for child processes that must start fresh
-  (switches read once per process) without regenerating it.
+  (switches read when the context is created) without regenerating it.
 """
 from __future__ import annotations
 

@@ -544,7 +544,7 @@ def test_binary_keys_right_after_frequent_conditions(ctx):
 
 @pytest.mark.parametrize("env", [{"RDFIND_B2_SPLIT": "2"}, {"RDFIND_B2_RADIX_MIN": "1"}], ids=["split", "radix"])
 def test_k2_split_forced_small_inputs(monkeypatch, env):
-    """The K2 paths of large inputs forced on small ones (read once per process: a child process): the sub-bucket split
+    """The K2 paths of large inputs forced on small ones (read when the context is created: a child process): the sub-bucket split
     (k_b2_split, RDFIND_B2_SPLIT=2) and the hash-prefix radix grouping of compact records (k_b2_emit +
     radix_partition_hashed, which inputs of 3n >= 2^27 records take: c3, c4; RDFIND_B2_RADIX_MIN=1) give the oracle's
     sets in every mode and c1/c5 samples' checksums."""
@@ -591,7 +591,7 @@ def test_failed_split_launch_is_an_error_not_a_fault():
     by RDFIND_B2_SPLIT=2) makes rdf_frequent_conditions fail with RDF_ERR_HIP before any kernel consumes the sub-bucket
     offsets it would have written -- the round-4 aperture violation was a count kernel reading such offsets (DESIGN.md
     section 10).  A context without the hook then runs normally in the same process.  Own process: both switches are
-    read once per process or per context."""
+    read when the context is created."""
     import json
     import subprocess
     import sys
@@ -912,22 +912,118 @@ def test_copy_cinds_decoded_matches_host_decode(ctx):
     np.testing.assert_array_equal(dev["support"], host["support"])
 
 
+_C1_TEXT = []
+
+
+def c1_text():
+    """c1 at 0.2 as N-Triples text (12.3 MB, 200,000 triples), built once per session."""
+    if not _C1_TEXT:
+        _C1_TEXT.append("".join(ln + "\n" for ln in dataset("c1", 0.2).lines()).encode())
+    return _C1_TEXT[0]
+
+
 def test_parse_scratch_released(ctx):
     """After rdf_parse_ntriples only the text and the term table stay resident: the parse scratch (~36 B per term
-    occurrence + the slot table) is released before discovery (rdf_device_bytes)."""
+    occurrence + the slot table) is released before discovery (rdf_device_bytes), and what stays is counted."""
     c = _lib.Context(0)
     try:
-        data = "".join(ln + "\n" for ln in synth.config("c1", 0.2).lines()).encode()
+        data = c1_text()
         before = c.device_bytes()
         n, v, _ = c.parse_ntriples(data)
         held = c.device_bytes() - before
+        print("parse: held", held, "text", len(data), "triples", n, "terms", v)
         # text + triples (12 B each) + term table (12 B per term) + small scans; the scratch alone would be
         # 3 * 36 B per line plus a 2^k * 8 B slot table
         assert held < len(data) + 16 * n + 16 * v + (1 << 22), (held, len(data), n, v)
+        assert held >= len(data), (held, len(data))  # the text is resident and counted
         c.run(10)
         assert c.cind_count() > 0
     finally:
         c.close()
+
+
+def test_distinct_buffers_counted_and_released():
+    """The --distinct-triples buffers (slot table, flags, positions, the second copy of the triples) are counted by
+    rdf_device_bytes and released by rdf_release_scratch; the compacted triples stay resident and still run."""
+    rng = np.random.default_rng(23)
+    arr = rng.integers(0, 12, size=(3000, 3), dtype=np.uint32)
+    arr = np.concatenate([arr, arr[:1500]])  # every row of the first half at least twice
+    n = arr.shape[0]
+    _, first = np.unique(arr, axis=0, return_index=True)
+    exp = arr[np.sort(first)]  # first occurrences, input order
+    with _lib.Context(0) as c:
+        c.set_triples(arr[:, 0], arr[:, 1], arr[:, 2], 12)
+        before = c.device_bytes()
+        kept, _ = c.distinct_triples()
+        grown = c.device_bytes() - before
+        c.release_scratch()
+        after = c.device_bytes()
+        print("distinct: n", n, "kept", kept, "grown", grown, "after release", after - before)
+        assert grown >= 12 * n, (grown, n)
+        assert after < before + 12 * n + (1 << 20), (after, before, n)
+        # everything but the resident input (three id arrays of the sizes set_triples allocated) is gone
+        assert after <= before, (after, before)
+        assert kept == exp.shape[0]
+        s, p, o = c.copy_triples(n)
+        np.testing.assert_array_equal(np.stack([s, p, o], axis=1), exp)
+        c.run(2)
+        want, _ = C.run_set(exp[:, 0], exp[:, 1], exp[:, 2], 12, 2, 1, True)
+        assert _lib.decoded_to_set(c.decoded_cinds()) == want
+
+
+def test_destroy_frees_what_parse_allocated():
+    """rdf_ctx_destroy frees the parsed text and the term table: eight create / parse / close cycles leave the card's
+    free memory where one warm-up cycle left it.  A context that kept its text (nbytes + 16 each) would take
+    8 * len(data); the bound is half of that."""
+    import ctypes
+
+    data = c1_text()
+
+    def free_bytes():
+        # hipMemGetInfo of the runtime the library itself runs on (found through the library's handle).  It is the figure
+        # torch.cuda.mem_get_info reports, but torch brings a second copy of the HIP runtime, which finds no GPU in a
+        # process where the library's copy has already opened it.
+        free, total = ctypes.c_size_t(), ctypes.c_size_t()
+        assert _lib.load().hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) == 0
+        return free.value
+
+    def cycle():
+        c = _lib.Context(0)
+        try:
+            c.parse_ntriples(data)
+        finally:
+            c.close()
+
+    cycle()
+    free0 = free_bytes()
+    for _ in range(8):
+        cycle()
+    free1 = free_bytes()
+    print("destroy: free before", free0, "after", free1, "drop", free0 - free1, "text", len(data))
+    assert free0 - free1 < 4 * len(data), (free0, free1, len(data))
+
+
+def test_switches_are_per_context(monkeypatch, capfd):
+    """The RDFIND_* switches are read when a context is created: two contexts of one process, created under
+    RDFIND_STAGE=1 and RDFIND_STAGE=0, each run their own light variant (RDFIND_DEBUG_LIGHT reports it) and both
+    match the oracle."""
+    d = dataset("c1", 0.05)
+    monkeypatch.setenv("RDFIND_DEBUG_LIGHT", "1")
+    monkeypatch.setenv("RDFIND_STAGE", "1")
+    a = _lib.Context(0)
+    monkeypatch.setenv("RDFIND_STAGE", "0")
+    b = _lib.Context(0)
+    try:
+        for c, stage in ((a, 1), (b, 0), (a, 1)):
+            capfd.readouterr()
+            c.set_triples(d.s, d.p, d.o, d.num_terms)
+            c.run(d.min_support)
+            err = capfd.readouterr().err
+            assert f"(stage {stage}" in err and f"(stage {1 - stage}" not in err, (stage, err[-500:])
+            assert_stream_matches(c, "c1", 0.05, what=f"stage {stage}")
+    finally:
+        a.close()
+        b.close()
 
 
 def test_early_handover_matches_plain_copy():

@@ -211,7 +211,7 @@ def test_light_variants_full_size(ctx, env):
     two, every light dependent verified on its own instead of once per class of equal group lists, or every list of
     any length looking for an equal one) each reproduce the c1 and c2 golden vectors (and c4 at 0.1 for the sweep, two-pass, occupancy and pivot
     switches).  The switches are read
-    once per process, so each combination runs in its own child process."""
+    when the context is created; each combination runs in its own child process."""
     import subprocess
     import sys
 
@@ -288,7 +288,7 @@ print(json.dumps({"bad": bad}))
 def test_two_light_passes_random(ctx, heavy_min):
     """The filter + verify light passes forced on random inputs (RDFIND_LIGHT2=1; LIGHT_PRE_MAX defers every chunk of
     a multi-chunk dependent) against the C oracle in three modes, with and without lowered heavy columns.  In its own
-    process: the switch is read once per process."""
+    process: the switch is read when the context is created."""
     import subprocess
     import sys
 
