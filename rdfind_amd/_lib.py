@@ -39,6 +39,16 @@ EXPORTED_SYMBOLS = (
 )
 RDF_NT_TABS = 1
 
+# the test-only entry points of rdfind_amd/csrc/test_abi.h (not part of the product ABI)
+TEST_SYMBOLS = ("rdf_test_scan", "rdf_test_scan_batch", "rdf_test_radix", "rdf_test_radix_passes", "rdf_test_paths")
+SCAN_U32_U32, SCAN_U32_U64, SCAN_U64_U64 = range(3)
+SCAN_DTYPES = {SCAN_U32_U32: (np.uint32, np.uint32), SCAN_U32_U64: (np.uint32, np.uint64),
+               SCAN_U64_U64: (np.uint64, np.uint64)}
+RADIX_SORT_BITS, RADIX_SORT_DROP, RADIX_PART_HASHED, RADIX_PART_U32 = range(4)
+K1_FORMS = {0: None, 1: "partitioned", 2: "radix", 3: "atomic"}
+K2_FORMS = {0: None, 1: "plain", 2: "split", 3: "radix", 4: "atomic"}
+K3_FORMS = {0: None, 1: "onepass", 2: "twopass"}
+
 # rdf_exchange ops (sharded mode, include/rdfind_hip.h)
 X_DONE, X_ALLREDUCE_SUM_U32, X_ALLREDUCE_SUM_U64, X_ALLREDUCE_MIN_U64, X_ALLGATHERV_U64, X_ALLTOALLV_U64 = range(6)
 MAX_RANKS = 64
@@ -69,6 +79,14 @@ class CindStats(ctypes.Structure):
                 ("ms_heavy", ctypes.c_float), ("n_heavy_candidates", ctypes.c_uint64),
                 ("n_class_members", ctypes.c_uint64), ("n_classes", ctypes.c_uint64), ("n_class_cinds", ctypes.c_uint64),
                 ("n_light_candidates", ctypes.c_uint64), ("n_light_entries", ctypes.c_uint64)]
+
+
+class PathReport(ctypes.Structure):
+    """rdf_test_path_report (rdfind_amd/csrc/test_abi.h)."""
+    _fields_ = [("k1_form", ctypes.c_uint32), ("k2_form", ctypes.c_uint32), ("k3_form", ctypes.c_uint32),
+                ("dense_on", ctypes.c_uint32), ("light_stage", ctypes.c_uint32), ("light_hiocc", ctypes.c_uint32),
+                ("n_dense", ctypes.c_uint64), ("n_dense_eligible", ctypes.c_uint64),
+                ("n_dedup_members", ctypes.c_uint64)]
 
 
 class ResultLayout(ctypes.Structure):
@@ -191,9 +209,19 @@ def load():
         "rdf_shard_step": (i32, [P, ctypes.POINTER(Exchange)]),
         "rdf_shard_export": (i32, [P, P]),
         "rdf_shard_import": (i32, [P, P, u64]),
+        # test_abi.h
+        "rdf_test_scan": (i32, [P, ctypes.c_int, P, u64, u32, u32, ctypes.c_int, ctypes.c_int, P, ctypes.POINTER(u64),
+                                ctypes.POINTER(u32)]),
+        "rdf_test_scan_batch": (i32, [P, ctypes.c_int, P, u64, u32, P, ctypes.POINTER(u32)]),
+        "rdf_test_radix": (i32, [P, ctypes.c_int, P, u64, ctypes.c_int, ctypes.c_int, u64, P, ctypes.POINTER(u64),
+                                 ctypes.POINTER(u32)]),
+        "rdf_test_radix_passes": (ctypes.c_int, [ctypes.c_int]),
+        "rdf_test_paths": (i32, [P, ctypes.POINTER(PathReport)]),
     }
     for name, (res, args) in sig.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None) if name in TEST_SYMBOLS else getattr(lib, name)
+        if fn is None:  # a dev variant (RDFIND_HIP_LIB) built before the test entry points existed
+            continue
         fn.restype = res
         fn.argtypes = args
     _lib = lib
@@ -253,6 +281,12 @@ class Context:
             self.close()
         except Exception:
             pass
+
+    def _test_fn(self, name):
+        fn = getattr(self.lib, name, None)
+        if fn is None:
+            raise RdfError(f"{LIB_PATH} has no {name}: built before the test entry points (csrc/test_abi.h); rebuild it")
+        return fn
 
     def _check(self, rc, what):
         if rc != 0:
@@ -421,6 +455,58 @@ class Context:
                     "rdf_last_stats")
         self.fc, self.groups, self.cinds = _struct_dict(fc), _struct_dict(gs), _struct_dict(cs)
         return self.groups, self.cinds
+
+    # -- test-only entry points (rdfind_amd/csrc/test_abi.h) ------------------------------------
+    # The primitives run on caller data in buffers fenced by canaries; each method returns the canaries' state with
+    # its result (a failed call raises RdfError; its canary state is then in ``self.test_canaries_ok``).
+    def test_scan(self, kind: int, values, in_skew=0, out_skew=0, in_place=False, want_total=True):
+        """Exclusive scan of ``values`` by the primitive of ``kind``: (out, total or None, canaries_ok)."""
+        ti, to = SCAN_DTYPES[kind]
+        a = np.ascontiguousarray(values, dtype=ti)
+        out = np.empty(a.shape[0], to)
+        total, ok = ctypes.c_uint64(), ctypes.c_uint32()
+        rc = self._test_fn("rdf_test_scan")(self.ptr, kind, a.ctypes.data, a.shape[0], in_skew, out_skew, int(in_place),
+                                    int(want_total), out.ctypes.data, ctypes.byref(total), ctypes.byref(ok))
+        self.test_canaries_ok = bool(ok.value)
+        self._check(rc, "rdf_test_scan")
+        return out, (int(total.value) if want_total else None), bool(ok.value)
+
+    def test_scan_batch(self, rows, skew_mask=0, k=None):
+        """exclusive_scan_u32_u64_batch of the rows of a 2-D uint32 array: (out[k, n + 1], canaries_ok).  ``k``
+        overrides the row count passed to the primitive (to ask for a count it must refuse)."""
+        a = np.ascontiguousarray(rows, dtype=np.uint32)
+        assert a.ndim == 2
+        k = a.shape[0] if k is None else k
+        out = np.empty((max(k, 0), a.shape[1] + 1), np.uint64)
+        ok = ctypes.c_uint32()
+        rc = self._test_fn("rdf_test_scan_batch")(self.ptr, k, a.ctypes.data, a.shape[1], skew_mask, out.ctypes.data,
+                                          ctypes.byref(ok))
+        self.test_canaries_ok = bool(ok.value)
+        self._check(rc, "rdf_test_scan_batch")
+        return out, bool(ok.value)
+
+    def test_radix(self, op: int, keys, lo=0, hi=64, hmask=(1 << 64) - 1):
+        """A radix primitive on ``keys`` (uint32 for RADIX_PART_U32, else uint64): (result, canaries_ok); the result
+        is the array the primitive's ``keys`` names afterwards (for RADIX_SORT_DROP: the kept keys only)."""
+        a = np.ascontiguousarray(keys, dtype=np.uint32 if op == RADIX_PART_U32 else np.uint64)
+        out = np.empty_like(a)
+        n_out, ok = ctypes.c_uint64(), ctypes.c_uint32()
+        rc = self._test_fn("rdf_test_radix")(self.ptr, op, a.ctypes.data, a.shape[0], lo, hi, hmask, out.ctypes.data,
+                                     ctypes.byref(n_out), ctypes.byref(ok))
+        self.test_canaries_ok = bool(ok.value)
+        self._check(rc, "rdf_test_radix")
+        return out[: n_out.value], bool(ok.value)
+
+    def test_paths(self) -> dict:
+        """Which alternative paths the last completed run took (rdf_test_paths): the K1 / K2 / K3 forms by name,
+        dense_on, light_stage, light_hiocc, n_dense, n_dense_eligible, n_dedup_members."""
+        r = PathReport()
+        self._check(self._test_fn("rdf_test_paths")(self.ptr, ctypes.byref(r)), "rdf_test_paths")
+        d = _struct_dict(r)
+        d["k1_form"], d["k2_form"], d["k3_form"] = K1_FORMS[r.k1_form], K2_FORMS[r.k2_form], K3_FORMS[r.k3_form]
+        for name in ("dense_on", "light_stage", "light_hiocc"):
+            d[name] = bool(d[name])
+        return d
 
     # -- sharded mode (driven by rdfind_amd.distributed.run_sharded) ---------------------------
     def shard_begin(self, rank: int, nranks: int, min_support: int, projection="spo", clean_implied=True,

@@ -12,6 +12,7 @@
 #include <unordered_map>
 
 #include "../../include/rdfind_hip.h"
+#include "test_abi.h"
 #include "primitives.hpp"
 #include "kernels.inl"
 #include "switches.hpp"
@@ -230,6 +231,9 @@ struct rdf_ctx : CtxBuffers {
     bool dense_on = false;
     u64 dwords = 0, n_dense = 0;
     bool dense_flagged = false;           // d_dense_flags numbered rows this run (d_dense_build fills them)
+    u64 n_dense_eligible = 0;             // groups d_dense_flags numbered (n_dense: the rows d_dense_build gave a bitmap)
+    // which alternative ran at the run's decision points (RDF_TEST_K1_* / K2_* / K3_*, test_abi.h; 0: none yet)
+    u32 path_k1 = 0, path_k2 = 0, path_k3 = 0;
     bool sig_on = false;  // lsig holds this run's signatures (RDFIND_SIG=0 turns the filter off)
     bool sig_packed = false;  // the packed light path tests them too (RDFIND_SIG=1; default 2: k_light only)
     bool piv2_on = false;     // piv2 holds this run's second pivots
@@ -906,6 +910,7 @@ static rdf_status fc_unary_part(rdf_ctx* c, const u32* s, const u32* p, const u3
     // they keep the partition passes (profiles/r06_k1_radix_ab.log).  RDFIND_U1_RADIX_MIN=<3n> replaces the rule
     const bool radix_rule = c->sw.u1_radix_min ? 3 * n >= c->sw.u1_radix_min : 3 * n >= U1_RADIX_MIN && NB * 4 > U1_RADIX_LDS;
     const bool radix = radix_rule && 3 * n < (1ull << 32) && K <= 0xffffffffull;
+    c->path_k1 = radix ? RDF_TEST_K1_RADIX : RDF_TEST_K1_PARTITIONED;
     const void* recs = nullptr;
     unsigned G = 1;
     if (radix) {
@@ -1019,6 +1024,7 @@ static rdf_status fc_unary(rdf_ctx* c, u64 nfreq[3]) {
     }
     // fallback (|V| beyond the partitioned range; RDFIND_COUNT_PATHS=atomic test hook): global-atomic counts,
     // then global ranks by one scan (boff = 0)
+    c->path_k1 = RDF_TEST_K1_ATOMIC;
     ENSURE(c, cnt, K * 4);
     HIP_TRY(c, hipMemsetAsync(c->cnt.p, 0, K * 4, st));
     HIP_TRY(c, hipMemsetAsync(c->boff.p, 0, (NR + 2) * 4, st));
@@ -1109,6 +1115,7 @@ static rdf_status fc_binary_part(rdf_ctx* c, const u32* s, const u32* p, const u
     const int split_mode = c->sw.b2_split;
     // large inputs: compact records grouped by hash prefix with the radix passes (k_b2_emit, radix_partition_hashed)
     if (split_mode != 0 && 3 * n >= c->sw.b2_radix_min && maxrec < (1ull << 32)) {
+        c->path_k2 = RDF_TEST_K2_RADIX;
         ENSURE(c, brkeys2, maxrec * 8);
         HIP_TRY(c, hipMemsetAsync(dscal(c, 2), 0, 8, st));
         hipLaunchKernelGGL(k_b2_emit, dim3(grid_for(n, RDF_BLOCK * PART_U, kGrid)), dim3(RDF_BLOCK), 0, st, s, p, o, n, V,
@@ -1151,6 +1158,7 @@ static rdf_status fc_binary_part(rdf_ctx* c, const u32* s, const u32* p, const u
     const u64* recs = c->brkeys.as<u64>();
     const u32* bstart = c->uhist.as<u32>();
     u32 NBc = NB2, Gc = G2;
+    c->path_k2 = sub ? RDF_TEST_K2_SPLIT : RDF_TEST_K2_PLAIN;
     if (sub) {
         NBc = NB2 << sub;
         Gc = 1;
@@ -1287,6 +1295,7 @@ static rdf_status fc_begin(rdf_ctx* c, uint32_t min_support) {
     c->n_rules = 0;
     c->class_pending = false;
     c->paged = false;
+    c->path_k1 = c->path_k2 = 0;
     for (int i = 0; i < RDF_NUM_TIMERS; ++i) c->tn[i] = 0;  // a failed run may have left segments behind
     c->pend_fc = c->pend_groups = c->pend_heavy = false;
     c->spare_fc = false;  // this stage's scratch is in use again
@@ -1330,7 +1339,10 @@ rdf_status rdf_frequent_conditions(rdf_ctx* c, uint32_t min_support, rdf_fc_stat
     tbegin(c, RDF_T_BINARY);
     u64 B = 0, nkeys = 0, S = 0;
     if (c->n && !c->sw.count_atomic) TRY(fc_binary_part(c, c->s, c->p, c->o, c->n, false, &B, &nkeys, &S));
-    else if (c->n) TRY(fc_binary_global(c, &B, &nkeys));
+    else if (c->n) {
+        c->path_k2 = RDF_TEST_K2_ATOMIC;
+        TRY(fc_binary_global(c, &B, &nkeys));
+    }
     TRY(fc_binary_index(c, B));
     tend(c, RDF_T_BINARY);
     TRY(fc_end(c));
@@ -1476,6 +1488,8 @@ static rdf_status g_record_bits(rdf_ctx* c) {
     c->spare_groups = false;  // a group build starts: its record buffers are in use
     c->jr_keep = false;
     c->dense_on = false;
+    c->n_dense = c->n_dense_eligible = c->n_dedup_members = 0;
+    c->path_k3 = 0;
     const u32 V = c->V ? c->V : 1;
     const u64 ncap = 2ull * c->U + c->B;  // compact candidate captures (k_frank_final)
     const int capbits = bits_for(ncap ? ncap - 1 : 0);
@@ -1543,6 +1557,7 @@ static rdf_status g_emit_range(rdf_ctx* c, int proj, JoinSel js, u64 cap_rec, u3
     // block counts; no padding reaches the sort.  c2 emit 0.86 -> 0.73 ms, sort 1.79 -> 1.71, c3 step 72.4 -> 69.9 ms
     // (profiles/r05_emit_onepass_ab.log).  RDFIND_EMIT_ONEPASS=0: the count pass + write pass with padding
     const bool onepass = c->sw.emit_onepass && cache == 0 && slot_cap >= 9 * n;
+    if (n) c->path_k3 = std::max<u32>(c->path_k3, onepass ? RDF_TEST_K3_ONEPASS : RDF_TEST_K3_TWOPASS);
     if (onepass && n) {
         u64* eoff = c->eblk.as<u64>() + (eg + 1ull);
         HIP_TRY(c, hipMemsetAsync(c->eblk.as<u64>() + eg, 0, 8, st));  // records emitted, repeats included
@@ -2347,6 +2362,7 @@ static rdf_status d_dense_flags(rdf_ctx* c) {
     const u64 G = c->G, C = c->C;
     c->dense_on = false;
     c->dense_flagged = false;
+    c->n_dense = c->n_dense_eligible = 0;
     const int div = c->sw.dense_div >= 0 ? c->sw.dense_div : DENSE_DIV_STAGE;  // RDFIND_DENSE: one divisor for every input
     if (div <= 0 || !G || !C) return RDF_OK;
     auto clampd = [&](u64 m) { return (u32)std::min<u64>(std::max<u64>(m, c->sw.dense_min), 0x7fffffffu); };
@@ -2369,6 +2385,7 @@ static rdf_status d_dense_build(rdf_ctx* c, CindView& v, u64 nrows) {
     v.gdrow = nullptr;
     v.dbits = nullptr;
     if (!c->dense_flagged || !nrows) return RDF_OK;
+    c->n_dense_eligible = nrows;
     const u64 G = c->G, C = c->C;
     const u64 dwords = ((C + 31) / 32 + 31) & ~31ull;  // rows start on 128-B lines
     u64 budget = c->sw.dense_bytes;
@@ -2396,6 +2413,7 @@ static rdf_status d_dense_build(rdf_ctx* c, CindView& v, u64 nrows) {
                        dwords, c->dbits_p);
     tend(c, RDF_T_LIGHT);
     c->dense_on = true;
+    c->n_dense = rows;
     c->dwords = dwords;
     v.gdrow = c->gdrow.as<u32>();
     v.dbits = c->dbits_p;
@@ -3669,6 +3687,7 @@ static rdf_status sh_phase10(rdf_ctx* c, rdf_exchange* req) {
     if (n && NB <= U2_MAXB && !c->sw.count_atomic) {
         TRY(fc_unary_part(c, s, p, o, n, ubits, NB, true));
     } else {
+        c->path_k1 = RDF_TEST_K1_ATOMIC;
         HIP_TRY(c, hipMemsetAsync(c->cntg.p, 0, K * 4, st));
         if (n)
             hipLaunchKernelGGL(k_unary_count, dim3(std::min<unsigned>(grid_for(n, RDF_BLOCK * 4), 1024)), dim3(RDF_BLOCK), 0,
@@ -5330,3 +5349,5 @@ rdf_status rdf_stage_times(rdf_ctx* c, float* ms3) {
 }
 
 }  // extern "C"
+
+#include "test_abi.inl"

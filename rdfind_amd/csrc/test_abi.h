@@ -1,0 +1,80 @@
+/* Test-only entry points of librdfind_hip.so (rdf_test_*): the scan and radix primitives of primitives.hip on
+ * caller-given data, and a report of the paths the last run took.  Not part of the product ABI
+ * (include/rdfind_hip.h): bound by rdfind_amd/_lib.py for tests/test_gpu_primitives.py and the forced-path tests.
+ *
+ * Every call runs on the context's stream with the context's workspace, touches no pipeline state (the stage and
+ * the last result stay) and fails with an rdf_status and rdf_last_error like the product calls.
+ *
+ * Canaries: each call allocates its device buffers itself, with RDF_TEST_CANARY elements of the byte pattern
+ * RDF_TEST_CANARY_BYTE directly before and directly after every range a primitive may write.  *canaries_ok = 1 when
+ * all of them (and, for the scans, the input the primitive must not change) are intact after the call; it is
+ * written whenever the buffers could be allocated, also when the primitive itself returned an error. */
+#ifndef RDFIND_TEST_ABI_H
+#define RDFIND_TEST_ABI_H
+
+#include "../../include/rdfind_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define RDF_TEST_CANARY 64
+#define RDF_TEST_CANARY_BYTE 0xA5
+
+/* rdf_test_scan kinds: input -> output element types */
+enum { RDF_TEST_SCAN_U32_U32 = 0, RDF_TEST_SCAN_U32_U64 = 1, RDF_TEST_SCAN_U64_U64 = 2 };
+
+/* Exclusive scan of in_host[0, n) into out_host[0, n); *total_out = the sum (read from the device only when
+ * want_total, else the primitive gets a null total pointer and *total_out is left alone).
+ * in_skew / out_skew: element offsets (0..3) of the device arrays from a 16-byte aligned address (0: the vector
+ * kernels may run, otherwise not).  in_place: out == in on the device (equal element types only; out_skew must equal
+ * in_skew) and the total goes to out[n], the way the pipeline's callers do it; otherwise the total has a buffer of
+ * its own. */
+rdf_status rdf_test_scan(rdf_ctx* ctx, int kind, const void* in_host, uint64_t n, uint32_t in_skew, uint32_t out_skew,
+                         int in_place, int want_total, void* out_host, uint64_t* total_out, uint32_t* canaries_ok);
+
+/* exclusive_scan_u32_u64_batch of k arrays of n elements: in_host = k rows of n uint32, out_host = k rows of n + 1
+ * uint64 (the last one the row's total).  skew_mask: bit j skews input j by one element, bit 4 + j output j.
+ * k outside 1..4 is passed through (the primitive must refuse it); at most 8. */
+#define RDF_TEST_BATCH_CAP 8
+rdf_status rdf_test_scan_batch(rdf_ctx* ctx, int k, const uint32_t* in_host, uint64_t n, uint32_t skew_mask,
+                               uint64_t* out_host, uint32_t* canaries_ok);
+
+/* rdf_test_radix ops */
+enum {
+    RDF_TEST_RADIX_SORT_BITS = 0,   /* radix_sort_u64_bits(lo, hi), uint64 keys */
+    RDF_TEST_RADIX_SORT_DROP = 1,   /* radix_sort_u64_drop(bits = hi), uint64 keys; lo ignored */
+    RDF_TEST_RADIX_PART_HASHED = 2, /* radix_partition_hashed(bits = hi, hmask), uint64 keys; lo ignored */
+    RDF_TEST_RADIX_PART_U32 = 3     /* radix_partition_u32(lo, hi), uint32 keys */
+};
+
+/* out_host[0, *n_out) = the buffer `keys` names after the primitive's swaps; *n_out = n, for SORT_DROP the kept keys.
+ * out_host holds n keys. */
+rdf_status rdf_test_radix(rdf_ctx* ctx, int op, const void* keys_host, uint64_t n, int lo, int hi, uint64_t hmask,
+                          void* out_host, uint64_t* n_out, uint32_t* canaries_ok);
+
+/* radix_sort_passes(bits) */
+int rdf_test_radix_passes(int bits);
+
+/* Paths of the last completed run (RDF_ERR_STATE without one).  0 in a form field: that stage made no choice
+ * (K2 and K3 of an input without triples). */
+enum { RDF_TEST_K1_PARTITIONED = 1, RDF_TEST_K1_RADIX = 2, RDF_TEST_K1_ATOMIC = 3 };
+enum { RDF_TEST_K2_PLAIN = 1, RDF_TEST_K2_SPLIT = 2, RDF_TEST_K2_RADIX = 3, RDF_TEST_K2_ATOMIC = 4 };
+enum { RDF_TEST_K3_ONEPASS = 1, RDF_TEST_K3_TWOPASS = 2 }; /* TWOPASS: some emission ran as count + write */
+
+typedef struct rdf_test_path_report {
+    uint32_t k1_form, k2_form, k3_form;
+    uint32_t dense_on;             /* the light pass read member bitmaps */
+    uint32_t light_stage;          /* the LDS-staging light kernel */
+    uint32_t light_hiocc;          /* the high-occupancy plain light kernel */
+    uint64_t n_dense;              /* light groups with a bitmap row */
+    uint64_t n_dense_eligible;     /* ... of those large enough for one (the byte budget may hold fewer) */
+    uint64_t n_dedup_members;      /* light dependents that took their class representative's refs */
+} rdf_test_path_report;
+
+rdf_status rdf_test_paths(rdf_ctx* ctx, rdf_test_path_report* out);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

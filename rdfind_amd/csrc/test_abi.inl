@@ -1,0 +1,198 @@
+// Test-only entry points (test_abi.h).  Included at the end of rdfind_hip.hip, which defines rdf_ctx; nothing in
+// the pipeline calls them.
+
+namespace {
+
+// A device array of `count` elements of `esz` bytes that starts `skew` elements past a 16-byte aligned address, with
+// RDF_TEST_CANARY pattern elements directly before and directly after it.  The whole allocation starts as the pattern.
+struct TestArr {
+    DevBuf buf;
+    size_t esz = 0, count = 0, off = 0;  // off: the array's byte offset in buf
+    hipError_t make(size_t elem_bytes, size_t elems, unsigned skew, hipStream_t st) {
+        esz = elem_bytes;
+        count = elems;
+        off = (RDF_TEST_CANARY + skew) * esz;  // (hipMalloc aligns to 256 B and 64 elements are a multiple of 16 B)
+        hipError_t e = buf.ensure(off + (count + RDF_TEST_CANARY) * esz);
+        if (e != hipSuccess) return e;
+        return hipMemsetAsync(buf.p, RDF_TEST_CANARY_BYTE, buf.cap, st);
+    }
+    char* data() const { return (char*)buf.p + off; }
+    ~TestArr() { buf.release(); }
+};
+
+static bool all_pattern(const unsigned char* p, size_t bytes) {
+    for (size_t i = 0; i < bytes; ++i)
+        if (p[i] != RDF_TEST_CANARY_BYTE) return false;
+    return true;
+}
+
+// *ok &= the canaries on both sides of a[0, a.count) are intact (call after the stream has drained)
+static hipError_t check_canaries(const TestArr& a, bool* ok) {
+    const size_t cb = RDF_TEST_CANARY * a.esz;
+    std::vector<unsigned char> h(2 * cb);
+    hipError_t e = hipMemcpy(h.data(), a.data() - cb, cb, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h.data() + cb, a.data() + a.count * a.esz, cb, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && !all_pattern(h.data(), h.size())) *ok = false;
+    return e;
+}
+
+// *ok &= a[0, elems) still holds `want` (want == nullptr: the fill pattern)
+static hipError_t check_contents(const TestArr& a, const void* want, size_t elems, bool* ok) {
+    if (!elems) return hipSuccess;
+    std::vector<unsigned char> h(elems * a.esz);
+    hipError_t e = hipMemcpy(h.data(), a.data(), h.size(), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && !(want ? memcmp(h.data(), want, h.size()) == 0 : all_pattern(h.data(), h.size()))) *ok = false;
+    return e;
+}
+
+static rdf_status prim_status(rdf_ctx* c, hipError_t e, const char* what) {
+    if (e == hipSuccess) return RDF_OK;
+    (void)hipGetLastError();
+    return fail(c, e == hipErrorOutOfMemory ? RDF_ERR_OOM : RDF_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+}  // namespace
+
+extern "C" {
+
+rdf_status rdf_test_scan(rdf_ctx* c, int kind, const void* in_host, uint64_t n, uint32_t in_skew, uint32_t out_skew,
+                         int in_place, int want_total, void* out_host, uint64_t* total_out, uint32_t* canaries_ok) {
+    if (!c) return RDF_ERR_ARG;
+    if (!canaries_ok || (n && (!in_host || !out_host)) || (want_total && !total_out))
+        return fail(c, RDF_ERR_ARG, "rdf_test_scan: null argument");
+    *canaries_ok = 0;
+    if (kind < RDF_TEST_SCAN_U32_U32 || kind > RDF_TEST_SCAN_U64_U64 || in_skew > 3 || out_skew > 3)
+        return fail(c, RDF_ERR_ARG, "rdf_test_scan: kind or skew out of range");
+    const size_t isz = kind == RDF_TEST_SCAN_U64_U64 ? 8 : 4, osz = kind == RDF_TEST_SCAN_U32_U32 ? 4 : 8;
+    if (in_place && (isz != osz || in_skew != out_skew))
+        return fail(c, RDF_ERR_ARG, "rdf_test_scan: in place needs equal element types and skews");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    TestArr in, out, tot;
+    const bool tail_total = in_place && want_total;  // the total at out[n]: one more element may be written
+    HIP_TRY(c, in.make(isz, n + (tail_total ? 1 : 0), in_skew, st));
+    if (!in_place) HIP_TRY(c, out.make(osz, n, out_skew, st));
+    if (!in_place && want_total) HIP_TRY(c, tot.make(osz, 1, 0, st));
+    if (n) HIP_TRY(c, hipMemcpyAsync(in.data(), in_host, n * isz, hipMemcpyHostToDevice, st));
+    char* d_out = in_place ? in.data() : out.data();
+    char* d_tot = !want_total ? nullptr : in_place ? in.data() + n * osz : tot.data();
+    hipError_t e = kind == RDF_TEST_SCAN_U32_U32   ? exclusive_scan_u32(c->ws, (const u32*)in.data(), (u32*)d_out, n, (u32*)d_tot, st)
+                   : kind == RDF_TEST_SCAN_U32_U64 ? exclusive_scan_u32_u64(c->ws, (const u32*)in.data(), (u64*)d_out, n, (u64*)d_tot, st)
+                                                   : exclusive_scan_u64(c->ws, (const u64*)in.data(), (u64*)d_out, n, (u64*)d_tot, st);
+    HIP_TRY(c, hipStreamSynchronize(st));
+    bool ok = true;
+    HIP_TRY(c, check_canaries(in, &ok));
+    if (!in_place) {
+        HIP_TRY(c, check_canaries(out, &ok));
+        HIP_TRY(c, check_contents(in, in_host, n, &ok));  // the input is read only
+        if (want_total) HIP_TRY(c, check_canaries(tot, &ok));
+    }
+    *canaries_ok = ok ? 1 : 0;
+    TRY(prim_status(c, e, "exclusive_scan"));
+    if (n) HIP_TRY(c, hipMemcpy(out_host, d_out, n * osz, hipMemcpyDeviceToHost));
+    if (want_total) {
+        u64 t = 0;  // (little endian: a 4-byte total lands in the low half)
+        HIP_TRY(c, hipMemcpy(&t, d_tot, osz, hipMemcpyDeviceToHost));
+        *total_out = t;
+    }
+    return RDF_OK;
+}
+
+rdf_status rdf_test_scan_batch(rdf_ctx* c, int k, const uint32_t* in_host, uint64_t n, uint32_t skew_mask,
+                               uint64_t* out_host, uint32_t* canaries_ok) {
+    if (!c) return RDF_ERR_ARG;
+    if (!canaries_ok || (k > 0 && ((n && !in_host) || !out_host))) return fail(c, RDF_ERR_ARG, "rdf_test_scan_batch: null argument");
+    *canaries_ok = 0;
+    if (k < 0 || k > RDF_TEST_BATCH_CAP) return fail(c, RDF_ERR_ARG, "rdf_test_scan_batch: k out of range");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const int nb = std::max(k, 1);  // (k = 0 still gets one pair of arrays to watch)
+    TestArr in[RDF_TEST_BATCH_CAP], out[RDF_TEST_BATCH_CAP];
+    const u32* ip[RDF_TEST_BATCH_CAP] = {};
+    u64* op[RDF_TEST_BATCH_CAP] = {};
+    for (int j = 0; j < nb; ++j) {
+        HIP_TRY(c, in[j].make(4, n, (skew_mask >> j) & 1u, st));
+        HIP_TRY(c, out[j].make(8, n + 1, (skew_mask >> (4 + j)) & 1u, st));
+        if (j < k && n) HIP_TRY(c, hipMemcpyAsync(in[j].data(), in_host + (u64)j * n, n * 4, hipMemcpyHostToDevice, st));
+        ip[j] = (const u32*)in[j].data();
+        op[j] = (u64*)out[j].data();
+    }
+    const hipError_t e = exclusive_scan_u32_u64_batch(c->ws, ip, op, k, n, st);
+    HIP_TRY(c, hipStreamSynchronize(st));
+    bool ok = true;
+    for (int j = 0; j < nb; ++j) {
+        HIP_TRY(c, check_canaries(in[j], &ok));
+        HIP_TRY(c, check_canaries(out[j], &ok));
+        if (j < k) HIP_TRY(c, check_contents(in[j], in_host + (u64)j * n, n, &ok));
+        if (e != hipSuccess) HIP_TRY(c, check_contents(out[j], nullptr, n + 1, &ok));  // a refused call writes nothing
+    }
+    *canaries_ok = ok ? 1 : 0;
+    TRY(prim_status(c, e, "exclusive_scan_u32_u64_batch"));
+    for (int j = 0; j < k; ++j)
+        HIP_TRY(c, hipMemcpy(out_host + (u64)j * (n + 1), out[j].data(), (n + 1) * 8, hipMemcpyDeviceToHost));
+    return RDF_OK;
+}
+
+rdf_status rdf_test_radix(rdf_ctx* c, int op, const void* keys_host, uint64_t n, int lo, int hi, uint64_t hmask,
+                          void* out_host, uint64_t* n_out, uint32_t* canaries_ok) {
+    if (!c) return RDF_ERR_ARG;
+    if (!canaries_ok || !n_out || (n && (!keys_host || !out_host))) return fail(c, RDF_ERR_ARG, "rdf_test_radix: null argument");
+    *canaries_ok = 0;
+    *n_out = 0;
+    if (op < RDF_TEST_RADIX_SORT_BITS || op > RDF_TEST_RADIX_PART_U32 || n >= (1ull << 32))
+        return fail(c, RDF_ERR_ARG, "rdf_test_radix: op or n out of range");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const size_t ksz = op == RDF_TEST_RADIX_PART_U32 ? 4 : 8;
+    TestArr a, b, kept;  // the passes write a and b in turn
+    HIP_TRY(c, a.make(ksz, n, 0, st));
+    HIP_TRY(c, b.make(ksz, n, 0, st));
+    HIP_TRY(c, kept.make(4, 1, 0, st));
+    if (n) HIP_TRY(c, hipMemcpyAsync(a.data(), keys_host, n * ksz, hipMemcpyHostToDevice, st));
+    u64 m = n;
+    const char* res = nullptr;
+    hipError_t e;
+    if (op == RDF_TEST_RADIX_PART_U32) {
+        u32 *keys = (u32*)a.data(), *tmp = (u32*)b.data();
+        e = radix_partition_u32(c->ws, keys, tmp, n, lo, hi, st);
+        res = (const char*)keys;
+    } else {
+        u64 *keys = (u64*)a.data(), *tmp = (u64*)b.data();
+        e = op == RDF_TEST_RADIX_SORT_BITS   ? radix_sort_u64_bits(c->ws, keys, tmp, n, lo, hi, st)
+            : op == RDF_TEST_RADIX_SORT_DROP ? radix_sort_u64_drop(c->ws, keys, tmp, n, hi, (u32*)kept.data(), &m, st)
+                                             : radix_partition_hashed(c->ws, keys, tmp, n, hi, hmask, st);
+        res = (const char*)keys;
+    }
+    HIP_TRY(c, hipStreamSynchronize(st));
+    bool ok = true;
+    HIP_TRY(c, check_canaries(a, &ok));
+    HIP_TRY(c, check_canaries(b, &ok));
+    HIP_TRY(c, check_canaries(kept, &ok));
+    *canaries_ok = ok ? 1 : 0;
+    TRY(prim_status(c, e, "radix primitive"));
+    if (m > n) return fail(c, RDF_ERR_HIP, "rdf_test_radix: more keys kept than given");
+    if (m) HIP_TRY(c, hipMemcpy(out_host, res, m * ksz, hipMemcpyDeviceToHost));
+    *n_out = m;
+    return RDF_OK;
+}
+
+int rdf_test_radix_passes(int bits) { return radix_sort_passes(bits); }
+
+rdf_status rdf_test_paths(rdf_ctx* c, rdf_test_path_report* out) {
+    if (!c || !out) return RDF_ERR_ARG;
+    if (c->stage < 4) return fail(c, RDF_ERR_STATE, "no completed run");
+    rdf_test_path_report r = {};
+    r.k1_form = c->path_k1;
+    r.k2_form = c->path_k2;
+    r.k3_form = c->path_k3;
+    r.dense_on = c->dense_on ? 1 : 0;
+    r.light_stage = c->light_stage ? 1 : 0;
+    r.light_hiocc = c->light_hiocc ? 1 : 0;
+    r.n_dense = c->n_dense;
+    r.n_dense_eligible = c->n_dense_eligible;
+    r.n_dedup_members = c->n_dedup_members;
+    *out = r;
+    return RDF_OK;
+}
+
+}  // extern "C"

@@ -56,6 +56,15 @@ def compact_matches(ctx, nv):
     return n == ctx.cind_count() and h == ctx.checksum()
 
 
+DEFAULT_FORMS = ("partitioned", "plain", "onepass")  # K1, K2, K3 of a small input with no switch set
+
+
+def forms(c):
+    """(K1, K2, K3) forms of the context's last run (rdf_test_paths)."""
+    t = c.test_paths()
+    return t["k1_form"], t["k2_form"], t["k3_form"]
+
+
 def test_random_parity_all_modes(ctx):
     rng = random.Random(11)
     for _ in range(150):
@@ -68,6 +77,7 @@ def test_random_parity_all_modes(ctx):
             assert gpu_set(ctx, arr, nv, ms, strategy, clean) == expected_set(arr, nv, ms, strategy, clean), \
                 (n, nv, ms, strategy, clean)
             assert compact_matches(ctx, nv)
+            assert forms(ctx) == DEFAULT_FORMS, (n, nv, ms)  # (no switch leaks into the default context)
 
 
 def test_projection_subsets(ctx):
@@ -179,6 +189,7 @@ def test_global_count_paths(ctx, monkeypatch):
                            dtype=np.uint32)
             for strategy, clean in ((1, True), (0, False)):
                 assert gpu_set(g, arr, nv, ms, strategy, clean) == expected_set(arr, nv, ms, strategy, clean)
+                assert forms(g)[:2] == ("atomic", "atomic"), (n, nv, ms)
         for cfg, scale in (("c1", 0.2), ("c5", 0.01)):
             d = dataset(cfg, scale)
             stats = []
@@ -187,6 +198,7 @@ def test_global_count_paths(ctx, monkeypatch):
                 c.run(d.min_support)
                 stats.append((dict(c.fc), c.checksum()))
             assert stats[0] == stats[1], cfg
+            assert forms(g)[:2] == ("atomic", "atomic") and forms(ctx)[:2] == DEFAULT_FORMS[:2], cfg
     finally:
         g.close()
 
@@ -207,6 +219,7 @@ def test_unary_radix_path_parity(ctx, monkeypatch):
                            dtype=np.uint32)
             for strategy, clean in ((1, True), (0, False)):
                 assert gpu_set(g, arr, nv, ms, strategy, clean) == expected_set(arr, nv, ms, strategy, clean)
+                assert forms(g)[0] == "radix", (n, nv, ms)
         for cfg, scale in (("c1", 0.2), ("c5", 0.01), ("c2", 0.05)):
             d = dataset(cfg, scale)
             stats = []
@@ -215,6 +228,7 @@ def test_unary_radix_path_parity(ctx, monkeypatch):
                 c.run(d.min_support)
                 stats.append((dict(c.fc), c.cind_count(), c.checksum()))
             assert stats[0] == stats[1], cfg
+            assert forms(g)[0] == "radix" and forms(ctx)[0] == "partitioned", cfg
     finally:
         g.close()
 
@@ -296,7 +310,8 @@ def test_dense_bitmap_paths_parity(monkeypatch, budget):
     """Every light group verified through its exact member bitmap (RDFIND_DENSE / RDFIND_DENSE_MIN test hooks: the
     dense-group path of the light kernels, serial, batched, packed and second-pivot checks), in every mode, and the
     heavy columns lowered too so that bitmaps and heavy masks mix.  With a bitmap budget of 3 rows (RDFIND_DENSE_BYTES)
-    the first groups get bitmaps and the rest keep their member lists, mixed within one dependent."""
+    the first groups get bitmaps and the rest keep their member lists, mixed within one dependent.  rdf_test_paths says
+    how many groups got a bitmap: all the eligible ones without a budget, three of them with it."""
     monkeypatch.setenv("RDFIND_DENSE", "1000000")
     monkeypatch.setenv("RDFIND_DENSE_MIN", "1")
     if budget:
@@ -306,6 +321,7 @@ def test_dense_bitmap_paths_parity(monkeypatch, budget):
         g = _lib.Context(0)
         try:
             rng = random.Random(300 + heavy_min)
+            n_dense = n_capped = 0
             for _ in range(30):
                 n = rng.randrange(20, 400)
                 nv = rng.randrange(4, 40)
@@ -315,11 +331,37 @@ def test_dense_bitmap_paths_parity(monkeypatch, budget):
                 for strategy, clean in MODES:
                     assert gpu_set(g, arr, nv, ms, strategy, clean) == expected_set(arr, nv, ms, strategy, clean), \
                         (n, nv, ms, strategy, clean, heavy_min)
+                    t = g.test_paths()
+                    n_dense += t["n_dense"]
+                    n_capped += 0 < t["n_dense"] < t["n_dense_eligible"]
+            print("dense paths: budget", budget, "heavy_min", heavy_min, "random inputs: n_dense", n_dense,
+                  "runs with bitmaps and lists mixed", n_capped)
+            assert n_dense > 0  # the random inputs' light passes read bitmaps
+            assert (n_capped > 0) == bool(budget)  # ... next to member lists under the budget only
             for cfg, scale in (("c5", 0.01), ("c1", 0.05), ("c4", 0.0003)):
                 d = dataset(cfg, scale)
                 g.set_triples(d.s, d.p, d.o, d.num_terms)
                 g.run(d.min_support)
                 assert_stream_matches(g, cfg, scale, what=heavy_min)
+                t = g.test_paths()
+                print("dense paths:", cfg, "n_dense", t["n_dense"], "of", t["n_dense_eligible"], "dense_on", t["dense_on"])
+                if not budget:  # every eligible group got its bitmap
+                    assert t["dense_on"] and t["n_dense"] == t["n_dense_eligible"] > 0, (cfg, t)
+                    continue
+                # 384 bytes hold three rows only up to 1024 captures: the samples have more, so under that budget they
+                # get at most one bitmap, mostly none.  Their mixed case needs three rows of their own size (a row is
+                # a bit per capture, padded to 128 bytes): a context of its own per sample
+                row_bytes = ((g.groups["n_captures"] + 31) // 32 + 31) // 32 * 32 * 4
+                assert t["n_dense"] == 384 // row_bytes < 3 < t["n_dense_eligible"], (cfg, t, row_bytes)
+                monkeypatch.setenv("RDFIND_DENSE_BYTES", str(3 * row_bytes))
+                with _lib.Context(0) as g3:
+                    monkeypatch.setenv("RDFIND_DENSE_BYTES", budget)
+                    g3.set_triples(d.s, d.p, d.o, d.num_terms)
+                    g3.run(d.min_support)
+                    assert_stream_matches(g3, cfg, scale, what=(heavy_min, "3 rows"))
+                    t = g3.test_paths()
+                    print("dense paths:", cfg, "3 rows of", row_bytes, "B: n_dense", t["n_dense"], "of", t["n_dense_eligible"])
+                    assert t["dense_on"] and t["n_dense"] == 3 < t["n_dense_eligible"], (cfg, t)
         finally:
             g.close()
 
@@ -561,6 +603,7 @@ from rdfind_amd import _lib
 from tests.test_gpu import MODES, expected_set
 from tests.parity import dataset, oracle_stream
 bad = []
+k2 = set()
 rng = random.Random(61)
 with _lib.Context(0) as g:
     for it in range(20):
@@ -569,21 +612,26 @@ with _lib.Context(0) as g:
         for strategy, clean in MODES:
             g.set_triples(arr[:, 0], arr[:, 1], arr[:, 2], nv)
             g.run(ms, "spo", clean, strategy)
+            k2.add(g.test_paths()["k2_form"])
             if _lib.decoded_to_set(g.decoded_cinds()) != expected_set(arr, nv, ms, strategy, clean):
                 bad.append((it, strategy, clean))
     for cfg, scale in (("c1", 0.05), ("c5", 0.01)):
         d = dataset(cfg, scale)
         g.set_triples(d.s, d.p, d.o, d.num_terms)
         g.run(d.min_support)
+        k2.add(g.test_paths()["k2_form"])
         e = oracle_stream(cfg, scale)
         if (g.cind_count(), g.checksum()) != (e["n_cinds"], e["checksum"]):
             bad.append(cfg)
-print(json.dumps({"bad": bad}))
+print(json.dumps({"bad": bad, "k2_forms": sorted(k2)}))
 """
     r = subprocess.run([sys.executable, "-c", child, root], env=dict(os.environ, **env), capture_output=True,
                        text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
-    assert json.loads(r.stdout.strip().splitlines()[-1])["bad"] == []
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["bad"] == []
+    # every run took the forced form (rdf_test_paths), not the plain one
+    assert out["k2_forms"] == ["split" if "RDFIND_B2_SPLIT" in env else "radix"]
 
 
 def test_failed_split_launch_is_an_error_not_a_fault():
@@ -1020,6 +1068,7 @@ def test_switches_are_per_context(monkeypatch, capfd):
             c.run(d.min_support)
             err = capfd.readouterr().err
             assert f"(stage {stage}" in err and f"(stage {1 - stage}" not in err, (stage, err[-500:])
+            assert c.test_paths()["light_stage"] == bool(stage)
             assert_stream_matches(c, "c1", 0.05, what=f"stage {stage}")
     finally:
         a.close()
@@ -1117,6 +1166,7 @@ def test_light_dedup_parity(monkeypatch, dedup, dup_min):
         g = _lib.Context(0)
         try:
             rng = random.Random(600 + int(heavy_min))
+            members = {mode: 0 for mode in MODES}
             for _ in range(30):
                 n = rng.randrange(1, 400)
                 nv = rng.randrange(2, 40)
@@ -1126,10 +1176,27 @@ def test_light_dedup_parity(monkeypatch, dedup, dup_min):
                 for strategy, clean in MODES:
                     assert gpu_set(g, arr, nv, ms, strategy, clean) == expected_set(arr, nv, ms, strategy, clean), \
                         (n, nv, ms, strategy, clean, dedup, heavy_min)
+                    members[(strategy, clean)] += g.test_paths()["n_dedup_members"]
+            print("dedup paths:", dedup, dup_min, "heavy_min", heavy_min, "random inputs' members by mode", members)
+            # strategy 0 verifies every dependent on its own whatever the switch says; so does RDFIND_LIGHT_DEDUP=0
+            assert members[(0, True)] == 0 and members[(0, False)] == 0
+            if dedup == "0":
+                assert sum(members.values()) == 0
+            elif dup_min == "1" and heavy_min == "64":
+                # every light dependent looks for an equal list, and some of these inputs have them.  (With
+                # RDFIND_HEAVY_MIN=2 these small inputs have none: a group shared by two dependents has two members and
+                # is heavy here, so no two dependents share a light group; the samples below still form classes)
+                assert members[(1, True)] > 0
             for cfg, scale in (("c1", 0.05), ("c5", 0.01), ("c2", 0.02)):
                 d = dataset(cfg, scale)
                 g.set_triples(d.s, d.p, d.o, d.num_terms)
                 g.run(d.min_support)
                 assert_stream_matches(g, cfg, scale, what=(dedup, heavy_min))
+                nm = g.test_paths()["n_dedup_members"]
+                print("dedup paths:", dedup, dup_min, "heavy_min", heavy_min, cfg, "members", nm)
+                if dedup == "0":
+                    assert nm == 0, cfg
+                elif dup_min == "1":  # every sample has dependents with equal group lists, at both heavy_min values
+                    assert nm > 0, cfg
         finally:
             g.close()
