@@ -142,11 +142,48 @@ rdf_status rdf_distinct_triples(rdf_ctx* ctx, uint64_t* n_distinct, float* ms);
 #define RDF_NT_TABS 1u                 /* --tabs: tab-separated terms */
 rdf_status rdf_parse_ntriples(rdf_ctx* ctx, const char* text, uint64_t nbytes, uint32_t flags, uint64_t* n_triples,
                               uint32_t* num_terms, float* ms);
-/* Uses the dictionary of the last rdf_parse_ntriples as the formatting dictionary (rdf_set_dictionary without a
- * host round trip); RDF_ERR_STATE if triples were set another way since. */
+/* Uses the dictionary of the last rdf_parse_ntriples (or of the last chunked parse, below) as the formatting
+ * dictionary (rdf_set_dictionary without a host round trip); RDF_ERR_STATE if triples were set another way since. */
 rdf_status rdf_set_dictionary_parsed(rdf_ctx* ctx);
-/* The dictionary of the last rdf_parse_ntriples: term id i is text[offsets[i] .. offsets[i] + lengths[i]). */
+/* The dictionary of the last parse: term id i is base[offsets[i] .. offsets[i] + lengths[i]).  After
+ * rdf_parse_ntriples base is the text that was parsed; after a chunked parse (rdf_parse_end) the offsets point
+ * into the term heap that rdf_copy_term_heap returns, not into any text. */
 rdf_status rdf_copy_terms(rdf_ctx* ctx, uint64_t* offsets, uint32_t* lengths, uint64_t cap, uint64_t* n_copied);
+
+/* Chunked N-Triples ingest: the same parse in several calls, against a dictionary that stays on the device between
+ * them, so that neither the host nor the GPU ever holds more than one window of text plus the distinct terms (the
+ * single call keeps the whole text in HBM and sizes one table for all term occurrences).
+ *   rdf_parse_begin   opens a parse (flags: RDF_NT_TABS).  reserve_triples > 0 allocates the triple arrays for that
+ *                     many rows up front; otherwise they grow geometrically.  The context holds no input until
+ *                     rdf_parse_end (stage 0: rdf_frequent_conditions returns RDF_ERR_STATE).
+ *   rdf_parse_chunk   parses one window: a run of whole lines.  A window that does not end in '\n' ends its last line
+ *                     where it ends.  An empty window, or one of comments and blank lines only, adds nothing but its
+ *                     lines to the line count.  "\r\n", '#', blank lines and tabs behave as in rdf_parse_ntriples.
+ *                     The optional outputs receive the totals so far.
+ *   rdf_parse_end     makes the parsed triples the resident input, exactly as rdf_parse_ntriples leaves them; the
+ *                     window scratch and the term table are released, the term heap stays as the dictionary.
+ * For any split of a text at line boundaries the triples (s, p, o, their order, n, num_terms) and the dictionary
+ * (term id -> bytes) are bit-identical to one rdf_parse_ntriples over the concatenation: ids follow first appearance.
+ * Limits hold per window (3 * lines < 2^32, window table <= 2^32 slots) and for the totals (n < 2^32 / 3 triples,
+ * num_terms < 2^30); the total number of term occurrences is not limited.
+ * A malformed line fails with RDF_ERR_ARG naming its 1-based line number in the whole input, and abandons the parse:
+ * the context holds no input, the parse buffers are released, and a new rdf_parse_begin may follow.  Any other failed
+ * chunk abandons it too, and so do rdf_set_triples*, rdf_parse_ntriples and rdf_shard_parse_begin called during an
+ * open parse, since they replace the input.  rdf_parse_chunk / rdf_parse_end without an open parse: RDF_ERR_STATE. */
+typedef struct {
+    uint64_t n_triples, n_terms, n_lines, n_chunks;
+    uint64_t heap_bytes;        /* bytes of the distinct terms kept in HBM */
+    uint64_t table_slots;       /* slots of the persistent term table at the end */
+    uint64_t n_table_growths;   /* times the table was rebuilt larger */
+    float ms;                   /* summed device time of the chunks */
+} rdf_parse_stats;
+rdf_status rdf_parse_begin(rdf_ctx* ctx, uint32_t flags, uint64_t reserve_triples);
+rdf_status rdf_parse_chunk(rdf_ctx* ctx, const char* text, uint64_t nbytes, uint64_t* n_triples_so_far,
+                           uint32_t* num_terms_so_far);
+rdf_status rdf_parse_end(rdf_ctx* ctx, rdf_parse_stats* stats /* may be null */);
+/* The term heap of the last chunked parse: copies min(cap, heap bytes) to out; *bytes receives the heap's size
+ * (call with cap = 0 to learn it).  RDF_ERR_STATE unless the resident dictionary comes from rdf_parse_end. */
+rdf_status rdf_copy_term_heap(rdf_ctx* ctx, char* out, uint64_t cap, uint64_t* bytes);
 
 /* Copies min(cap, n) resident triples to host arrays (e.g. after rdf_distinct_triples). */
 rdf_status rdf_copy_triples(rdf_ctx* ctx, uint32_t* s, uint32_t* p, uint32_t* o, uint64_t cap, uint64_t* n_copied);

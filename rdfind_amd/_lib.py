@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = (
     "rdf_discover_cinds_paged", "rdf_next_page", "rdf_shard_parse_begin", "rdf_shard_dictionary_begin", "rdf_num_terms",
     "rdf_dictionary_terms", "rdf_copy_result_refs", "rdf_release_scratch", "rdf_set_handover",
     "rdf_copy_result_refs_async", "rdf_handover_wait", "rdf_set_result_form", "rdf_heavy_chunk_count",
-    "rdf_copy_result_heavy",
+    "rdf_copy_result_heavy", "rdf_parse_begin", "rdf_parse_chunk", "rdf_parse_end", "rdf_copy_term_heap",
 )
 RDF_NT_TABS = 1
 
@@ -62,6 +62,13 @@ class FcStats(ctypes.Structure):
     _fields_ = [("min_support", ctypes.c_uint32), ("n_ar_suppressed", ctypes.c_uint32),
                 ("n_frequent_unary", ctypes.c_uint64 * 3), ("n_binary_keys", ctypes.c_uint64),
                 ("n_frequent_binary", ctypes.c_uint64)]
+
+
+class ParseStats(ctypes.Structure):
+    """rdf_parse_stats: the totals of a chunked parse (rdf_parse_end)."""
+    _fields_ = [("n_triples", ctypes.c_uint64), ("n_terms", ctypes.c_uint64), ("n_lines", ctypes.c_uint64),
+                ("n_chunks", ctypes.c_uint64), ("heap_bytes", ctypes.c_uint64), ("table_slots", ctypes.c_uint64),
+                ("n_table_growths", ctypes.c_uint64), ("ms", ctypes.c_float)]
 
 
 class GroupStats(ctypes.Structure):
@@ -161,6 +168,10 @@ def load():
                                      ctypes.POINTER(ctypes.c_float)]),
         "rdf_copy_terms": (i32, [P, P, P, u64, ctypes.POINTER(u64)]),
         "rdf_set_dictionary_parsed": (i32, [P]),
+        "rdf_parse_begin": (i32, [P, u32, u64]),
+        "rdf_parse_chunk": (i32, [P, ctypes.c_char_p, u64, ctypes.POINTER(u64), ctypes.POINTER(u32)]),
+        "rdf_parse_end": (i32, [P, ctypes.POINTER(ParseStats)]),
+        "rdf_copy_term_heap": (i32, [P, P, u64, ctypes.POINTER(u64)]),
         "rdf_frequent_conditions": (i32, [P, u32, ctypes.POINTER(FcStats)]),
         "rdf_build_capture_groups": (i32, [P, ctypes.c_char_p, ctypes.POINTER(GroupStats)]),
         "rdf_discover_cinds": (i32, [P, u32, ctypes.POINTER(CindStats)]),
@@ -328,6 +339,38 @@ class Context:
         self._parsed = data
         return int(n.value), int(v.value), float(ms.value)
 
+    def parse_begin(self, tabs: bool = False, reserve_triples: int = 0):
+        """Opens a chunked parse (rdf_parse_begin): the input follows in :meth:`parse_chunk` calls, and the dictionary
+        stays on the device between them.  ``reserve_triples`` allocates the triple arrays up front."""
+        self._check(self.lib.rdf_parse_begin(self.ptr, RDF_NT_TABS if tabs else 0, reserve_triples), "rdf_parse_begin")
+        self._parsed = b""
+
+    def parse_chunk(self, data: bytes):
+        """One window of whole lines (rdf_parse_chunk); returns the totals so far, (n_triples, num_terms)."""
+        n, v = ctypes.c_uint64(), ctypes.c_uint32()
+        self._check(self.lib.rdf_parse_chunk(self.ptr, data, len(data), ctypes.byref(n), ctypes.byref(v)),
+                    "rdf_parse_chunk")
+        return int(n.value), int(v.value)
+
+    def parse_end(self) -> dict:
+        """Closes the chunked parse (rdf_parse_end): its triples become the resident input.  Returns the stats
+        (n_triples, n_terms, n_lines, n_chunks, heap_bytes, table_slots, n_table_growths, ms).  The offsets of
+        :meth:`parsed_terms` then point into the term heap, which that call fetches (rdf_copy_term_heap)."""
+        st = ParseStats()
+        self._check(self.lib.rdf_parse_end(self.ptr, ctypes.byref(st)), "rdf_parse_end")
+        self.num_terms = int(st.n_terms)
+        self._parsed = None  # the term heap, fetched when parsed_terms asks for it
+        return {k: (float(st.ms) if k == "ms" else int(getattr(st, k))) for k, _ in ParseStats._fields_}
+
+    def parse_windows(self, windows, tabs: bool = False):
+        """A chunked parse of an iterable of ``bytes`` windows (e.g. ``ntriples.iter_windows``); returns
+        (n_triples, num_terms, device ms) like :meth:`parse_ntriples`."""
+        self.parse_begin(tabs=tabs)
+        for w in windows:
+            self.parse_chunk(w)
+        st = self.parse_end()
+        return st["n_triples"], st["n_terms"], st["ms"]
+
     def parsed_terms(self):
         """The device dictionary of the last parse as (heap bytes, uint64 offsets[V + 1]): term i is
         heap[offsets[i]:offsets[i + 1]] (UTF-8)."""
@@ -339,6 +382,13 @@ class Context:
         ln64 = ln.astype(np.int64)
         offsets = np.zeros(v + 1, np.uint64)
         np.cumsum(ln64, out=offsets[1:])
+        if self._parsed is None:
+            size = ctypes.c_uint64()
+            self._check(self.lib.rdf_copy_term_heap(self.ptr, None, 0, ctypes.byref(size)), "rdf_copy_term_heap")
+            heap = np.empty(int(size.value), np.uint8)
+            self._check(self.lib.rdf_copy_term_heap(self.ptr, heap.ctypes.data, heap.shape[0], ctypes.byref(size)),
+                        "rdf_copy_term_heap")
+            self._parsed = heap.tobytes()
         src = np.frombuffer(self._parsed, np.uint8)
         pos = np.arange(int(offsets[-1]), dtype=np.int64) + np.repeat(off.astype(np.int64) - offsets[:-1].astype(np.int64),
                                                                        ln64)

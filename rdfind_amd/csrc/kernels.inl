@@ -4034,13 +4034,20 @@ __device__ inline bool nt_equal(const unsigned char* __restrict__ text, u64 a, u
     return true;
 }
 
-// dictionary table: entries fingerprint<<32 | occurrence; the slot of a term ends holding its first occurrence
+// the fingerprint bits of a table entry that are compared before the bytes: the top `bits` (0..32) of the hash
+static inline u64 nt_fp_mask(int bits) { return bits <= 0 ? 0 : ~0ull << (64 - (bits < 32 ? bits : 32)); }
+
+// dictionary table: entries fingerprint<<32 | occurrence; the slot of a term ends holding its first occurrence.
+// valid[k / VDIV] selects the occurrences that take part (3: a flag per line; 1: a flag per occurrence, the chunked
+// parse's misses); an occupied slot is byte-compared when its fingerprint agrees in the bits of fpmask.
+template <u32 VDIV>
 __global__ __launch_bounds__(RDF_BLOCK) void k_nt_dict_insert(const unsigned char* __restrict__ text,
                                                               const u64* __restrict__ tstart, const u32* __restrict__ tlen,
                                                               const u32* __restrict__ valid, u64 nocc,
-                                                              const u64* __restrict__ hv, u64* table, u64 mask, u32* slot) {
+                                                              const u64* __restrict__ hv, u64* table, u64 mask, u32* slot,
+                                                              u64 fpmask) {
     for (u64 k = (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; k < nocc; k += (u64)gridDim.x * RDF_BLOCK) {
-        if (!valid[k / 3]) continue;
+        if (!valid[k / VDIV]) continue;
         const u64 a = tstart[k];
         const u32 n = tlen[k];
         const u64 h0 = hv[k];
@@ -4052,7 +4059,7 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_nt_dict_insert(const unsigned cha
                 cur = atomicCAS(&table[h], EMPTY64, e);
                 if (cur == EMPTY64) break;
             }
-            if ((cur >> 32) == (e >> 32)) {
+            if (!((cur ^ e) & fpmask)) {
                 const u32 j = (u32)cur;
                 if (tlen[j] == n && nt_equal(text, tstart[j], a, n)) {
                     if (cur > e) atomicMin(&table[h], e);
@@ -4065,12 +4072,13 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_nt_dict_insert(const unsigned cha
 }
 
 // per occurrence: its term's first occurrence (rep) and whether it is that first occurrence
+template <u32 VDIV>
 __global__ __launch_bounds__(RDF_BLOCK) void k_nt_dict_rep(const u32* __restrict__ valid, u64 nocc,
                                                            const u32* __restrict__ slot, const u64* __restrict__ table,
                                                            u32* rep, u32* first) {
     for (u64 k = (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; k < nocc; k += (u64)gridDim.x * RDF_BLOCK) {
         u32 r = (u32)k, f = 0;
-        if (valid[k / 3]) {
+        if (valid[k / VDIV]) {
             r = (u32)table[slot[k]];
             f = r == (u32)k;
         }
@@ -4096,6 +4104,147 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_nt_assign(const u64* __restrict__
             term_off[id] = tstart[k];
             term_len[id] = tlen[k];
         }
+    }
+}
+
+// ---- chunked ingest (rdf_parse_begin / rdf_parse_chunk / rdf_parse_end): the input arrives as windows of whole lines
+// and the dictionary lives on the device between them.  Kept between the windows: the bytes of the distinct terms
+// (the term heap, term id i at heap[term_off[i], +term_len[i]), padded like the text), the 64-bit hash of each term
+// and an open-addressing table of fingerprint << 32 | term id over all terms so far.  A window is tokenized by the
+// kernels above; its occurrences are looked up in the table (read-only), the misses are deduplicated among themselves
+// by the window-local table (k_nt_dict_insert<1> over the miss flags), and the first occurrences of the new terms get
+// the next ids in their order of appearance: exactly the ids one parse of the whole text assigns.
+
+static constexpr u32 NT_MISS = 0xffffffffu;
+
+// byte equality of ta[a, a+n) and tb[b, b+n), four bytes per step (both buffers 4-B aligned and padded by 16 bytes)
+__device__ inline bool nt_equal2(const unsigned char* __restrict__ ta, u64 a, const unsigned char* __restrict__ tb, u64 b,
+                                 u32 n) {
+    const u32* wa = (const u32*)ta;
+    const u32* wb = (const u32*)tb;
+    u32 i = 0;
+    for (; i + 4 <= n; i += 4)
+        if (nt_word(wa, a + i) != nt_word(wb, b + i)) return false;
+    if (i < n) {
+        const u32 m = (1u << (8 * (n - i))) - 1u;
+        if ((nt_word(wa, a + i) ^ nt_word(wb, b + i)) & m) return false;
+    }
+    return true;
+}
+
+// per occurrence of a valid line: the id of its term if an earlier window brought it (gid), else NT_MISS and miss = 1.
+// A hit needs the fingerprint bits of fpmask, the length and the bytes (window text against the heap) to agree.
+// The table is only read here, so this pass cannot race with k_nt_publish.
+__global__ __launch_bounds__(RDF_BLOCK) void k_nt_lookup(const unsigned char* __restrict__ text,
+                                                         const u64* __restrict__ tstart, const u32* __restrict__ tlen,
+                                                         const u32* __restrict__ valid, u64 nocc,
+                                                         const u64* __restrict__ hv, const u64* __restrict__ table, u64 mask,
+                                                         u64 fpmask, const unsigned char* __restrict__ heap,
+                                                         const u64* __restrict__ term_off, const u32* __restrict__ term_len,
+                                                         u32* gid, u32* miss) {
+    for (u64 k = (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; k < nocc; k += (u64)gridDim.x * RDF_BLOCK) {
+        const bool live = valid[k / 3] != 0;
+        u64 hit = EMPTY64;  // the slot of the term's entry
+        if (live) {
+            const u64 a = tstart[k], h0 = hv[k];
+            const u32 n = tlen[k];
+            u64 h = h0 & mask;
+            for (u64 probe = 0; probe <= mask && hit == EMPTY64; ++probe, h = (h + 1) & mask) {
+                const u64 cur = table[h];
+                if (cur == EMPTY64) break;
+                if ((cur ^ h0) & fpmask) continue;
+                const u32 j = (u32)cur;
+                if (term_len[j] == n && nt_equal2(text, a, heap, term_off[j], n)) hit = h;
+            }
+        }
+        // (the id is read from the slot again: carried out of the loop in a register, it was lost on the comparison's
+        // tail path in the code the compiler generated)
+        const u32 id = hit != EMPTY64 ? (u32)table[hit] : NT_MISS;
+        gid[k] = id;
+        miss[k] = live && id == NT_MISS;
+    }
+}
+
+// per occurrence: the length of its term if it is the first occurrence of a new term, else 0 (scanned: the new
+// terms' byte offsets behind the heap's end, in id order)
+__global__ __launch_bounds__(RDF_BLOCK) void k_nt_new_len(const u32* __restrict__ first, const u32* __restrict__ tlen, u64 nocc,
+                                                          u32* nlen) {
+    for (u64 k = (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; k < nocc; k += (u64)gridDim.x * RDF_BLOCK)
+        nlen[k] = first[k] ? tlen[k] : 0;
+}
+
+// the new terms' rows (id = v0 + rank among the window's first occurrences): heap offset, length, hash; src[rank]:
+// where the term's bytes start in the window text
+__global__ __launch_bounds__(RDF_BLOCK) void k_nt_append(const u32* __restrict__ first, const u32* __restrict__ fid,
+                                                         const u64* __restrict__ tstart, const u32* __restrict__ tlen,
+                                                         const u64* __restrict__ hv, const u64* __restrict__ noff, u64 nocc,
+                                                         u32 v0, u64 heap0, u64* term_off, u32* term_len, u64* term_hv,
+                                                         u64* src) {
+    for (u64 k = (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; k < nocc; k += (u64)gridDim.x * RDF_BLOCK) {
+        if (!first[k]) continue;
+        const u32 r = fid[k];
+        term_off[v0 + r] = heap0 + noff[k];
+        term_len[v0 + r] = tlen[k];
+        term_hv[v0 + r] = hv[k];
+        src[r] = tstart[k];
+    }
+}
+
+// the new terms' bytes, window text -> heap[heap0, heap1).  The destination is one contiguous run in id order, so a
+// thread owns one aligned 4-B word of it (a wave stores 256 contiguous bytes) and finds the term of its first byte
+// by binary search in the new terms' offsets noff[0, vnew) (ascending; = term_off + v0); neighbouring lanes read
+// neighbouring text bytes.  The word holding heap0 keeps its bytes below heap0; bytes from heap1 on are zero (padding).
+__global__ __launch_bounds__(RDF_BLOCK) void k_nt_append_bytes(const unsigned char* __restrict__ text,
+                                                               const u64* __restrict__ src, const u64* __restrict__ noff,
+                                                               u64 vnew, u64 heap0, u64 heap1, u32* heap_words) {
+    const u64 w0 = heap0 >> 2, w1 = (heap1 + 3) >> 2;
+    for (u64 w = w0 + (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; w < w1; w += (u64)gridDim.x * RDF_BLOCK) {
+        u64 q = 4 * w;
+        u32 word = q < heap0 ? heap_words[w] : 0;
+        if (q < heap0) {
+            word &= (1u << (8 * (heap0 - q))) - 1u;
+            q = heap0;
+        }
+        u64 lo = 0, hi = vnew;  // r: the last term with noff[r] <= q
+        while (lo < hi) {
+            const u64 mid = (lo + hi) >> 1;
+            if (noff[mid] <= q) lo = mid + 1; else hi = mid;
+        }
+        u64 r = lo - 1;
+        for (; q < 4 * w + 4 && q < heap1; ++q) {
+            while (r + 1 < vnew && noff[r + 1] <= q) ++r;
+            word |= (u32)text[src[r] + (q - noff[r])] << (8 * (q & 3));
+        }
+        heap_words[w] = word;
+    }
+}
+
+// ids [id0, id1) into the persistent table, from the stored hashes: all terms are distinct, so an insert is a CAS on
+// the first empty slot of the probe sequence and no bytes are compared
+__global__ __launch_bounds__(RDF_BLOCK) void k_nt_publish(const u64* __restrict__ term_hv, u64 id0, u64 id1, u64* table,
+                                                          u64 mask, u64 fpmask) {
+    for (u64 i = id0 + (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; i < id1; i += (u64)gridDim.x * RDF_BLOCK) {
+        const u64 h0 = term_hv[i], e = (h0 & fpmask & 0xffffffff00000000ull) | i;
+        u64 h = h0 & mask;
+        for (u64 probe = 0; probe <= mask; ++probe, h = (h + 1) & mask) {
+            if (__hip_atomic_load(&table[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != EMPTY64) continue;
+            if (atomicCAS(&table[h], EMPTY64, e) == EMPTY64) break;
+        }
+    }
+}
+
+// triples of the window at rows n0 + lpos: a hit carries its id, a miss the id of its term's first occurrence
+__global__ __launch_bounds__(RDF_BLOCK) void k_nt_assign_chunk(const u32* __restrict__ valid, const u32* __restrict__ lpos,
+                                                               u64 nocc, const u32* __restrict__ gid,
+                                                               const u32* __restrict__ rep, const u32* __restrict__ fid,
+                                                               u32 v0, u64 n0, u32* s, u32* p, u32* o) {
+    for (u64 k = (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; k < nocc; k += (u64)gridDim.x * RDF_BLOCK) {
+        const u64 l = k / 3;
+        if (!valid[l]) continue;
+        const u32 g = gid[k], id = g != NT_MISS ? g : v0 + fid[rep[k]];
+        const u32 t = (u32)(k - 3 * l);
+        const u64 row = n0 + lpos[l];
+        (t == 0 ? s : t == 1 ? p : o)[row] = id;
     }
 }
 

@@ -25,7 +25,8 @@ using namespace rdf;
 // so c->rec and ENSURE(c, rec, ...) name them), their iteration (for_each_buf: destroy, rdf_device_bytes, the memory
 // report) and the release lists all come from this table.  Lifetime classes:
 //   INPUT         the resident input, its dictionary and the parsed text: kept until the context is destroyed
-//   PARSE         scratch of rdf_parse_ntriples, released when it returns
+//   PARSE         scratch of rdf_parse_ntriples, released when it returns; of a chunked parse (rdf_parse_begin), released
+//                 by rdf_parse_end and whenever the open parse is abandoned
 //   SPARE_FC      the frequent-condition stage's record scratch, spare once that stage is done (reclaim_spare)
 //   SPARE_GROUPS  the group build's record and sort buffers, spare once the groups are built
 //   SPARE_X       the exchange buffers, spare from the routing of the triples to the end of the group build
@@ -44,6 +45,12 @@ using namespace rdf;
     /* ... line / term arrays, dictionary table (~36 B per term occurrence + the slot table) */ \
     B(PARSE, ncnt) B(PARSE, ncoff) B(PARSE, nlstart) B(PARSE, ntstart) B(PARSE, ntlen) B(PARSE, nvalid) B(PARSE, nlpos) \
     B(PARSE, nhv) B(PARSE, nslot) B(PARSE, ntab) B(PARSE, nrep) B(PARSE, nfirst) B(PARSE, nfid) \
+    /* chunked ingest (rdf_parse_begin .. rdf_parse_end).  Kept between the windows: the term heap (the distinct terms' */ \
+    /* bytes; nterm_off points into it afterwards), the terms' hashes, the table of fingerprint << 32 | term id. */ \
+    /* Per window: its text, the occurrences' ids from earlier windows and miss flags, the new terms' lengths, heap */ \
+    /* offsets and text positions */ \
+    B(INPUT, ntheap) B(INPUT, nthash) B(INPUT, nptab) \
+    B(PARSE, nwin) B(PARSE, ngid) B(PARSE, nmiss) B(PARSE, nnlen) B(PARSE, nnoff) B(PARSE, nsrc) \
     /* frequent conditions */ \
     B(RUN, frank) B(RUN, fval) B(RUN, fext) \
     B(RUN, cnt) B(SPARE_FC, tkeys) B(RUN, tcnt) B(RUN, bkeys) B(RUN, bkeys_tmp) B(RUN, lkeys) B(RUN, lvals) B(RUN, flags) \
@@ -166,6 +173,12 @@ struct rdf_ctx : CtxBuffers {
 
     u64 n_terms_parsed = 0;  // rows of nterm_off/nterm_len (rdf_copy_terms)
     bool parsed_dict = false;  // the resident triples' ids are the last parse's dictionary
+    bool dict_in_heap = false;  // nterm_off points into ntheap (chunked parse), not into ntext
+    // chunked parse (rdf_parse_begin .. rdf_parse_end): totals so far
+    bool parse_open = false;
+    u32 parse_flags = 0;
+    u64 pc_n = 0, pc_V = 0, pc_lines = 0, pc_chunks = 0, pc_heap = 0, pc_slots = 0, pc_growths = 0;
+    float pc_ms = 0;
     const u32 *s = nullptr, *p = nullptr, *o = nullptr;
     u64 n = 0;
     u32 V = 0;
@@ -668,9 +681,29 @@ rdf_status rdf_release_scratch(rdf_ctx* c) {
     return RDF_OK;
 }
 
+// An open chunked parse (rdf_parse_begin) ends without a result: on a failed chunk, and when another call replaces the
+// input.  The context holds no input afterwards (stage 0); the window scratch and the partial dictionary are released.
+static void parse_abandon(rdf_ctx* c) {
+    if (!c->parse_open) return;
+    (void)hipStreamSynchronize(c->stream);
+    for_each_buf(c, [](DevBuf& b, const BufEntry& e) {
+        if (e.cls == BUF_PARSE) b.release();
+    });
+    c->ntheap.release();
+    c->nthash.release();
+    c->nptab.release();
+    (void)hipGetLastError();
+    c->parse_open = false;
+    c->parsed_dict = false;
+    c->dict_in_heap = false;
+    c->n_terms_parsed = 0;
+    c->stage = 0;
+}
+
 rdf_status rdf_set_triples(rdf_ctx* c, const uint32_t* s, const uint32_t* p, const uint32_t* o, uint64_t n,
                            uint32_t num_terms) {
     if (!c || (n && (!s || !p || !o))) return fail(c, RDF_ERR_ARG, "null triple arrays");
+    parse_abandon(c);
     rdf_status st = check_terms(c, n, num_terms);
     if (st) return st;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -700,6 +733,7 @@ rdf_status rdf_set_triples(rdf_ctx* c, const uint32_t* s, const uint32_t* p, con
 rdf_status rdf_set_triples_device(rdf_ctx* c, const uint32_t* s, const uint32_t* p, const uint32_t* o, uint64_t n,
                                   uint32_t num_terms) {
     if (!c || (n && (!s || !p || !o))) return fail(c, RDF_ERR_ARG, "null triple arrays");
+    parse_abandon(c);
     if (c) TRY(hv_wait(c, true));
     rdf_status st = check_terms(c, n, num_terms);
     if (st) return st;
@@ -790,6 +824,11 @@ rdf_status rdf_parse_ntriples(rdf_ctx* c, const char* text, uint64_t nbytes, uin
     if (!c || (nbytes && !text)) return fail(c, RDF_ERR_ARG, "null text");
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(hv_wait(c, true));
+    parse_abandon(c);
+    if (c->dict_in_heap) {  // the term table is rewritten below: a chunked parse's dictionary ends here
+        c->ntheap.release();
+        c->dict_in_heap = c->parsed_dict = false;
+    }
     hipStream_t st = c->stream;
     const unsigned char* dtext = nullptr;
     ENSURE(c, ntext, nbytes + 16);  // 16-B loads of the last tile stay inside the buffer
@@ -830,9 +869,10 @@ rdf_status rdf_parse_ntriples(rdf_ctx* c, const char* text, uint64_t nbytes, uin
     ENSURE(c, nfirst, nocc * 4);
     ENSURE(c, nfid, nocc * 4);
     HIP_TRY(c, hipMemsetAsync(c->ntab.p, 0xff, T * 8, st));
-    hipLaunchKernelGGL(k_nt_dict_insert, dim3(go), dim3(RDF_BLOCK), 0, st, dtext, c->ntstart.as<u64>(), c->ntlen.as<u32>(),
-                       c->nvalid.as<u32>(), nocc, c->nhv.as<u64>(), c->ntab.as<u64>(), T - 1, c->nslot.as<u32>());
-    hipLaunchKernelGGL(k_nt_dict_rep, dim3(go), dim3(RDF_BLOCK), 0, st, c->nvalid.as<u32>(), nocc, c->nslot.as<u32>(),
+    hipLaunchKernelGGL(k_nt_dict_insert<3>, dim3(go), dim3(RDF_BLOCK), 0, st, dtext, c->ntstart.as<u64>(), c->ntlen.as<u32>(),
+                       c->nvalid.as<u32>(), nocc, c->nhv.as<u64>(), c->ntab.as<u64>(), T - 1, c->nslot.as<u32>(),
+                       nt_fp_mask(32));
+    hipLaunchKernelGGL(k_nt_dict_rep<3>, dim3(go), dim3(RDF_BLOCK), 0, st, c->nvalid.as<u32>(), nocc, c->nslot.as<u32>(),
                        c->ntab.as<u64>(), c->nrep.as<u32>(), c->nfirst.as<u32>());
     HIP_TRY(c, hipMemsetAsync(dscal(c, 3), 0, 8, st));
     HIP_TRY(c, exclusive_scan_u32(c->ws, c->nfirst.as<u32>(), c->nfid.as<u32>(), nocc, (u32*)dscal(c, 3), st));
@@ -876,7 +916,8 @@ rdf_status rdf_parse_ntriples(rdf_ctx* c, const char* text, uint64_t nbytes, uin
     return RDF_OK;
 }
 
-// Term table of the last rdf_parse_ntriples: byte offset (into the parsed text) and length of term id i.
+// Term table of the last parse: byte offset and length of term id i.  The offsets point into the parsed text after
+// rdf_parse_ntriples, into the term heap (rdf_copy_term_heap) after a chunked parse.
 rdf_status rdf_copy_terms(rdf_ctx* c, uint64_t* offsets, uint32_t* lengths, uint64_t cap, uint64_t* n_copied) {
     if (!c) return RDF_ERR_ARG;
     const u64 n = std::min<u64>(cap, c->n_terms_parsed);
@@ -888,6 +929,283 @@ rdf_status rdf_copy_terms(rdf_ctx* c, uint64_t* offsets, uint32_t* lengths, uint
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (n_copied) *n_copied = n;
+    return RDF_OK;
+}
+
+// ---- chunked ingest: the input in windows of whole lines against a dictionary that stays on the device between the
+// calls (the reference reads its input as splits and never holds the text: FLK/persistence/MultiFileTextInputFormat
+// .java:49-100).  Neither side ever holds more than one window of text plus the distinct terms; ids, triples and
+// dictionary equal those of one rdf_parse_ntriples over the concatenation (kernels.inl, "chunked ingest").
+
+// buffers that keep their contents while they grow: doubled, so a long run of windows copies each row O(1) times
+static rdf_status grow_keep_geo(rdf_ctx* c, DevBuf* b, u64 bytes, const char* what) {
+    if (b->p && bytes <= b->cap) return RDF_OK;
+    const u64 want = std::max<u64>(bytes, 2 * (u64)b->cap);
+    hipError_t e = b->grow_keep(want, c->stream);
+    if (e == hipErrorOutOfMemory && want > bytes) e = b->grow_keep(bytes, c->stream);
+    if (e == hipErrorOutOfMemory && reclaim_spare(c, b)) e = b->grow_keep(bytes, c->stream);
+    if (e != hipSuccess)
+        return fail(c, e == hipErrorOutOfMemory ? RDF_ERR_OOM : RDF_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    mem_track(c);
+    return RDF_OK;
+}
+// ... and end at exactly the size one ENSURE would have given them (the slack of the doubling goes back)
+static rdf_status fit_keep(rdf_ctx* c, DevBuf* b, u64 bytes, const char* what) {
+    const size_t want = (size_t)std::max<u64>(bytes, 256);
+    if (b->p && b->cap == want) return RDF_OK;
+    void* q = nullptr;
+    hipError_t e = hipMalloc(&q, want);
+    if (e == hipSuccess && b->p && bytes) {
+        e = hipMemcpyAsync(q, b->p, std::min<u64>(bytes, b->cap), hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+    if (e != hipSuccess) {
+        if (q) (void)hipFree(q);
+        (void)hipGetLastError();
+        return fail(c, e == hipErrorOutOfMemory ? RDF_ERR_OOM : RDF_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    }
+    b->release();
+    b->p = q;
+    b->cap = want;
+    return RDF_OK;
+}
+#define GROW_KEEP(ctx, buf, bytes) TRY(grow_keep_geo(ctx, &(ctx)->buf, (u64)(bytes), "growing " #buf))
+#define FIT_KEEP(ctx, buf, bytes) TRY(fit_keep(ctx, &(ctx)->buf, (u64)(bytes), "fitting " #buf))
+
+rdf_status rdf_parse_begin(rdf_ctx* c, uint32_t flags, uint64_t reserve_triples) {
+    if (!c) return RDF_ERR_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    TRY(hv_wait(c, true));
+    parse_abandon(c);
+    TRY(check_terms(c, reserve_triples, 0));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    release_run_buffers(c, reserve_triples);
+    // the previous input's dictionary goes: its text is the largest thing a context holds after a parse
+    c->ntext.release();
+    c->ntheap.release();
+    c->stage = 0;
+    c->paged = false;
+    c->parsed_dict = false;
+    c->dict_in_heap = false;
+    c->ingest_sharded = false;
+    c->n_terms_parsed = 0;
+    const u64 slots = next_pow2(std::max<u64>(c->sw.nt_dict_slots, 2));
+    if (slots > (1ull << 32)) return fail(c, RDF_ERR_LIMIT, "the term table has at most 2^32 slots");
+    ENSURE(c, nptab, slots * 8);
+    HIP_TRY(c, hipMemsetAsync(c->nptab.p, 0xff, slots * 8, c->stream));
+    ENSURE(c, ntheap, 16);
+    HIP_TRY(c, hipMemsetAsync(c->ntheap.p, 0, 16, c->stream));
+    if (reserve_triples) {
+        ENSURE(c, ts, reserve_triples * 4);
+        ENSURE(c, tp, reserve_triples * 4);
+        ENSURE(c, to, reserve_triples * 4);
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->parse_open = true;
+    c->parse_flags = flags;
+    c->pc_n = c->pc_V = c->pc_lines = c->pc_chunks = c->pc_heap = c->pc_growths = 0;
+    c->pc_slots = slots;
+    c->pc_ms = 0;
+    return RDF_OK;
+}
+
+static rdf_status parse_chunk_body(rdf_ctx* c, const char* text, u64 nbytes) {
+    hipStream_t st = c->stream;
+    c->pc_chunks++;
+    if (!nbytes) return RDF_OK;
+    ENSURE(c, nwin, nbytes + 16);  // 16-B loads of the last tile and nt_word stay inside the buffer
+    HIP_TRY(c, hipMemcpyAsync(c->nwin.p, text, nbytes, hipMemcpyHostToDevice, st));
+    const unsigned char* dtext = (const unsigned char*)c->nwin.p;
+    HIP_TRY(c, hipEventRecord(c->ev[6], st));
+    // lines, line starts, terms: as in rdf_parse_ntriples
+    const u64 nchunks = std::max<u64>((nbytes + NT_CHUNK - 1) / NT_CHUNK, 1);
+    ENSURE(c, ncnt, nchunks * 4);
+    ENSURE(c, ncoff, nchunks * 8);
+    const unsigned gc = (unsigned)std::min<u64>(nchunks, kGrid);
+    hipLaunchKernelGGL(k_nt_count_lines, dim3(gc), dim3(RDF_BLOCK), 0, st, dtext, nbytes, nchunks, c->ncnt.as<u32>());
+    HIP_TRY(c, exclusive_scan_u32_u64(c->ws, c->ncnt.as<u32>(), c->ncoff.as<u64>(), nchunks, dscal(c, 0), st));
+    u64 newlines = 0;
+    TRY(read_u64(c, dscal(c, 0), &newlines));
+    // a window that does not end in '\n' ends its last line where it ends; after a final '\n' the tokenizer sees one
+    // more, empty line, which is not a line of the input
+    const u64 nlines = newlines + 1, nocc = 3 * nlines, window_lines = newlines + (text[nbytes - 1] != '\n');
+    if (nocc >= 0xffffffffull) return fail(c, RDF_ERR_LIMIT, "too many lines in one window (3 * lines must be < 2^32)");
+    ENSURE(c, nlstart, nlines * 8);
+    hipLaunchKernelGGL(k_nt_line_starts, dim3(gc), dim3(RDF_BLOCK), 0, st, dtext, nbytes, nchunks, c->ncoff.as<u64>(),
+                       c->nlstart.as<u64>());
+    ENSURE(c, ntstart, nocc * 8);
+    ENSURE(c, nhv, nocc * 8);
+    ENSURE(c, ntlen, nocc * 4);
+    ENSURE(c, nvalid, nlines * 4);
+    ENSURE(c, nlpos, nlines * 4);
+    HIP_TRY(c, hipMemsetAsync(dscal(c, 1), 0xff, 8, st));
+    const unsigned gl = grid_for(nlines, RDF_BLOCK, kGrid), go = grid_for(nocc, RDF_BLOCK, kGrid);
+    hipLaunchKernelGGL(k_nt_tokenize, dim3(gl), dim3(RDF_BLOCK), 0, st, dtext, nbytes, c->nlstart.as<u64>(), nlines,
+                       (int)(c->parse_flags & RDF_NT_TABS), c->ntstart.as<u64>(), c->ntlen.as<u32>(), c->nhv.as<u64>(),
+                       c->nvalid.as<u32>(), dscal(c, 1));
+    HIP_TRY(c, hipMemsetAsync(dscal(c, 2), 0, 8, st));
+    HIP_TRY(c, exclusive_scan_u32(c->ws, c->nvalid.as<u32>(), c->nlpos.as<u32>(), nlines, (u32*)dscal(c, 2), st));
+    // terms of the earlier windows: hits carry their id
+    const u64 fpmask = nt_fp_mask(c->sw.nt_fp_bits);
+    ENSURE(c, ngid, nocc * 4);
+    ENSURE(c, nmiss, nocc * 4);
+    hipLaunchKernelGGL(k_nt_lookup, dim3(go), dim3(RDF_BLOCK), 0, st, dtext, c->ntstart.as<u64>(), c->ntlen.as<u32>(),
+                       c->nvalid.as<u32>(), nocc, c->nhv.as<u64>(), c->nptab.as<u64>(), c->pc_slots - 1, fpmask,
+                       (const unsigned char*)c->ntheap.p, c->nterm_off.as<u64>(), c->nterm_len.as<u32>(), c->ngid.as<u32>(),
+                       c->nmiss.as<u32>());
+    // the misses among themselves: first occurrences of the new terms and their ranks
+    const u64 T = next_pow2(2 * nocc);
+    if (T > (1ull << 32)) return fail(c, RDF_ERR_LIMIT, "too many terms per window (use smaller windows)");
+    ENSURE(c, ntab, T * 8);
+    ENSURE(c, nslot, nocc * 4);
+    ENSURE(c, nrep, nocc * 4);
+    ENSURE(c, nfirst, nocc * 4);
+    ENSURE(c, nfid, nocc * 4);
+    ENSURE(c, nnlen, nocc * 4);
+    ENSURE(c, nnoff, nocc * 8);
+    HIP_TRY(c, hipMemsetAsync(c->ntab.p, 0xff, T * 8, st));
+    hipLaunchKernelGGL(k_nt_dict_insert<1>, dim3(go), dim3(RDF_BLOCK), 0, st, dtext, c->ntstart.as<u64>(), c->ntlen.as<u32>(),
+                       c->nmiss.as<u32>(), nocc, c->nhv.as<u64>(), c->ntab.as<u64>(), T - 1, c->nslot.as<u32>(), fpmask);
+    hipLaunchKernelGGL(k_nt_dict_rep<1>, dim3(go), dim3(RDF_BLOCK), 0, st, c->nmiss.as<u32>(), nocc, c->nslot.as<u32>(),
+                       c->ntab.as<u64>(), c->nrep.as<u32>(), c->nfirst.as<u32>());
+    HIP_TRY(c, hipMemsetAsync(dscal(c, 3), 0, 8, st));
+    HIP_TRY(c, exclusive_scan_u32(c->ws, c->nfirst.as<u32>(), c->nfid.as<u32>(), nocc, (u32*)dscal(c, 3), st));
+    hipLaunchKernelGGL(k_nt_new_len, dim3(go), dim3(RDF_BLOCK), 0, st, c->nfirst.as<u32>(), c->ntlen.as<u32>(), nocc,
+                       c->nnlen.as<u32>());
+    HIP_TRY(c, exclusive_scan_u32_u64(c->ws, c->nnlen.as<u32>(), c->nnoff.as<u64>(), nocc, dscal(c, 4), st));
+    u64 sc[4];
+    TRY(read_multi(c, {{dscal(c, 1), 8}, {dscal(c, 2), 8}, {dscal(c, 3), 8}, {dscal(c, 4), 8}}, sc));
+    if (sc[0] != ~0ull)
+        return fail(c, RDF_ERR_ARG, "malformed N-Triples line " + std::to_string(c->pc_lines + sc[0] + 1));
+    const u64 nv = sc[1], vnew = sc[2], nb = sc[3];
+    const u64 n0 = c->pc_n, v0 = c->pc_V, n1 = n0 + nv, v1 = v0 + vnew, heap0 = c->pc_heap, heap1 = heap0 + nb;
+    TRY(check_terms(c, n1, (u32)std::min<u64>(v1, 0xffffffffull)));
+    GROW_KEEP(c, ts, n1 * 4);
+    GROW_KEEP(c, tp, n1 * 4);
+    GROW_KEEP(c, to, n1 * 4);
+    if (vnew) {
+        GROW_KEEP(c, nterm_off, v1 * 8);
+        GROW_KEEP(c, nterm_len, v1 * 4);
+        GROW_KEEP(c, nthash, v1 * 8);
+        GROW_KEEP(c, ntheap, heap1 + 16);
+        ENSURE(c, nsrc, vnew * 8);
+        hipLaunchKernelGGL(k_nt_append, dim3(go), dim3(RDF_BLOCK), 0, st, c->nfirst.as<u32>(), c->nfid.as<u32>(),
+                           c->ntstart.as<u64>(), c->ntlen.as<u32>(), c->nhv.as<u64>(), c->nnoff.as<u64>(), nocc, (u32)v0, heap0,
+                           c->nterm_off.as<u64>(), c->nterm_len.as<u32>(), c->nthash.as<u64>(), c->nsrc.as<u64>());
+        const u64 words = ((heap1 + 3) >> 2) - (heap0 >> 2);
+        if (words)
+            hipLaunchKernelGGL(k_nt_append_bytes, dim3(grid_for(words, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, dtext,
+                               c->nsrc.as<u64>(), c->nterm_off.as<u64>() + v0, vnew, heap0, heap1, c->ntheap.as<u32>());
+        // the table holds every term at a load of at most 1/2; a larger one is rebuilt from the stored hashes
+        u64 id0 = v0;
+        if (2 * v1 > c->pc_slots) {
+            c->pc_slots = next_pow2(2 * v1);
+            c->pc_growths++;
+            ENSURE(c, nptab, c->pc_slots * 8);
+            HIP_TRY(c, hipMemsetAsync(c->nptab.p, 0xff, c->pc_slots * 8, st));
+            id0 = 0;
+        }
+        hipLaunchKernelGGL(k_nt_publish, dim3(grid_for(v1 - id0, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st,
+                           c->nthash.as<u64>(), id0, v1, c->nptab.as<u64>(), c->pc_slots - 1, fpmask);
+    }
+    if (nv)
+        hipLaunchKernelGGL(k_nt_assign_chunk, dim3(go), dim3(RDF_BLOCK), 0, st, c->nvalid.as<u32>(), c->nlpos.as<u32>(), nocc,
+                           c->ngid.as<u32>(), c->nrep.as<u32>(), c->nfid.as<u32>(), (u32)v0, n0, c->ts.as<u32>(),
+                           c->tp.as<u32>(), c->to.as<u32>());
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev[7], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    float ms = 0;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
+    c->pc_ms += ms;
+    c->pc_n = n1;
+    c->pc_V = v1;
+    c->pc_heap = heap1;
+    c->pc_lines += window_lines;
+    return RDF_OK;
+}
+
+rdf_status rdf_parse_chunk(rdf_ctx* c, const char* text, uint64_t nbytes, uint64_t* n_triples_so_far,
+                           uint32_t* num_terms_so_far) {
+    if (!c) return RDF_ERR_ARG;
+    if (!c->parse_open) return fail(c, RDF_ERR_STATE, "rdf_parse_begin must be called first");
+    rdf_status rs = nbytes && !text ? fail(c, RDF_ERR_ARG, "null text") : RDF_OK;
+    if (!rs) {
+        hipError_t e = hipSetDevice(c->device);
+        rs = e == hipSuccess ? parse_chunk_body(c, text, nbytes) : fail(c, RDF_ERR_HIP, hipGetErrorString(e));
+    }
+    if (rs) {
+        parse_abandon(c);  // (the message of the failure stays)
+        return rs;
+    }
+    if (n_triples_so_far) *n_triples_so_far = c->pc_n;
+    if (num_terms_so_far) *num_terms_so_far = (u32)c->pc_V;
+    return RDF_OK;
+}
+
+static rdf_status parse_end_body(rdf_ctx* c) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // what stays is what rdf_parse_ntriples leaves, with the term heap in the text's place
+    for_each_buf(c, [](DevBuf& b, const BufEntry& e) {
+        if (e.cls == BUF_PARSE) b.release();
+    });
+    c->nptab.release();
+    c->nthash.release();
+    FIT_KEEP(c, ts, c->pc_n * 4);
+    FIT_KEEP(c, tp, c->pc_n * 4);
+    FIT_KEEP(c, to, c->pc_n * 4);
+    FIT_KEEP(c, nterm_off, c->pc_V * 8);
+    FIT_KEEP(c, nterm_len, c->pc_V * 4);
+    FIT_KEEP(c, ntheap, c->pc_heap + 16);
+    return RDF_OK;
+}
+
+rdf_status rdf_parse_end(rdf_ctx* c, rdf_parse_stats* stats) {
+    if (!c) return RDF_ERR_ARG;
+    if (!c->parse_open) return fail(c, RDF_ERR_STATE, "rdf_parse_begin must be called first");
+    const rdf_status rs = parse_end_body(c);
+    if (rs) {
+        parse_abandon(c);
+        return rs;
+    }
+    c->parse_open = false;
+    c->s = c->ts.as<u32>();
+    c->p = c->tp.as<u32>();
+    c->o = c->to.as<u32>();
+    c->n = c->pc_n;
+    c->V = (u32)c->pc_V;
+    c->stage = 1;
+    c->paged = false;
+    c->n_terms_parsed = c->pc_V;
+    c->parsed_dict = true;
+    c->dict_in_heap = true;
+    c->ingest_sharded = false;
+    if (stats) {
+        memset(stats, 0, sizeof(*stats));
+        stats->n_triples = c->pc_n;
+        stats->n_terms = c->pc_V;
+        stats->n_lines = c->pc_lines;
+        stats->n_chunks = c->pc_chunks;
+        stats->heap_bytes = c->pc_heap;
+        stats->table_slots = c->pc_slots;
+        stats->n_table_growths = c->pc_growths;
+        stats->ms = c->pc_ms;
+    }
+    return RDF_OK;
+}
+
+// The bytes of the distinct terms of the last chunked parse: term id i is heap[offsets[i], offsets[i] + lengths[i])
+// with the arrays of rdf_copy_terms.  *bytes is the heap's size, whatever cap allowed to copy.
+rdf_status rdf_copy_term_heap(rdf_ctx* c, char* out, uint64_t cap, uint64_t* bytes) {
+    if (!c) return RDF_ERR_ARG;
+    if (!c->parsed_dict || !c->dict_in_heap)
+        return fail(c, RDF_ERR_STATE, "the resident dictionary does not come from a chunked parse (rdf_parse_end)");
+    const u64 n = std::min<u64>(cap, c->pc_heap);
+    if (n && !out) return fail(c, RDF_ERR_ARG, "null heap buffer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (n) HIP_TRY(c, ctx_copy(c, out, c->ntheap.p, n, hipMemcpyDeviceToHost));
+    if (bytes) *bytes = c->pc_heap;
     return RDF_OK;
 }
 
@@ -4539,10 +4857,10 @@ static rdf_status sh_phase22(rdf_ctx* c, rdf_exchange* req) {
     HIP_TRY(c, hipMemsetAsync(c->rtab.p, 0xff, T * 8, st));
     const unsigned g = grid_for(std::max<u64>(m, 1), RDF_BLOCK, kGrid);
     if (m) {
-        hipLaunchKernelGGL(k_nt_dict_insert, dim3(g), dim3(RDF_BLOCK), 0, st, (const unsigned char*)c->own_text.p,
+        hipLaunchKernelGGL(k_nt_dict_insert<3>, dim3(g), dim3(RDF_BLOCK), 0, st, (const unsigned char*)c->own_text.p,
                            c->rts.as<u64>(), c->rlen.as<u32>(), c->rvalid.as<u32>(), m, c->rhv.as<u64>(), c->rtab.as<u64>(),
-                           T - 1, c->rslot.as<u32>());
-        hipLaunchKernelGGL(k_nt_dict_rep, dim3(g), dim3(RDF_BLOCK), 0, st, c->rvalid.as<u32>(), m, c->rslot.as<u32>(),
+                           T - 1, c->rslot.as<u32>(), nt_fp_mask(32));
+        hipLaunchKernelGGL(k_nt_dict_rep<3>, dim3(g), dim3(RDF_BLOCK), 0, st, c->rvalid.as<u32>(), m, c->rslot.as<u32>(),
                            c->rtab.as<u64>(), c->rrep.as<u32>(), c->rfirst.as<u32>());
     }
     HIP_TRY(c, exclusive_scan_u32(c->ws, c->rfirst.as<u32>(), c->rfid.as<u32>(), m, c->rfid.as<u32>() + m, st));
@@ -4719,6 +5037,7 @@ rdf_status rdf_shard_parse_begin(rdf_ctx* c, uint32_t rank, uint32_t nranks, con
                                  uint32_t flags, uint64_t* n_triples) {
     if (!c) return RDF_ERR_ARG;
     if (c) TRY(hv_wait(c, true));
+    parse_abandon(c);
     if (nranks < 1 || nranks > RDF_MAX_RANKS || rank >= nranks) return fail(c, RDF_ERR_ARG, "invalid rank / nranks");
     uint64_t n = 0;
     u32 Vl = 0;
@@ -5209,7 +5528,8 @@ rdf_status rdf_set_dictionary(rdf_ctx* c, const char* heap, uint64_t heap_bytes,
     return RDF_OK;
 }
 
-// The dictionary of the last rdf_parse_ntriples as the formatting dictionary, built in HBM (no host copy).
+// The dictionary of the last rdf_parse_ntriples (or of the last chunked parse, whose terms lie in the term heap) as
+// the formatting dictionary, built in HBM (no host copy).
 rdf_status rdf_set_dictionary_parsed(rdf_ctx* c) {
     if (!c) return RDF_ERR_ARG;
     if (!c->parsed_dict) return fail(c, RDF_ERR_STATE, "the resident triples do not come from rdf_parse_ntriples");
@@ -5223,8 +5543,8 @@ rdf_status rdf_set_dictionary_parsed(rdf_ctx* c) {
     ENSURE(c, dheap, std::max<u64>(total, 1));
     if (V)
         hipLaunchKernelGGL(k_nt_dict_gather, dim3(grid_for(V, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st,
-                           (const unsigned char*)c->ntext.p, c->nterm_off.as<u64>(), c->dtoff.as<u64>(), V,
-                           c->dheap.as<char>());
+                           (const unsigned char*)(c->dict_in_heap ? c->ntheap.p : c->ntext.p), c->nterm_off.as<u64>(),
+                           c->dtoff.as<u64>(), V, c->dheap.as<char>());
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(st));
     c->dict_terms = V;

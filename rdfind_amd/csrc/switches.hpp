@@ -51,6 +51,11 @@ static inline RankPhase rank_phase(const char* v) {  // "rank:phase"; anything e
        "0: K2 never groups its records by hash prefix (no k_b2_emit / k_b2_split)") \
     SW(b2_radix_min, u64, B2_RADIX_MIN, "RDFIND_B2_RADIX_MIN", strtoull(v, nullptr, 10), TEST, \
        "3n from which K2 groups compact records with the radix passes") \
+    /* chunked ingest */ \
+    SW(nt_dict_slots, u64, 1ull << 16, "RDFIND_NT_DICT_SLOTS", positive_or(v, s.nt_dict_slots), TEST, \
+       "=<pow2>: initial slots of the chunked parse's persistent term table (small: tiny inputs rebuild it several times)") \
+    SW(nt_fp_bits, int, 32, "RDFIND_NT_FP_BITS", std::max(0, std::min(atoi(v), 32)), TEST, \
+       "=<0..32>: fingerprint bits the chunked parse compares before the bytes (0: every occupied slot is byte-compared)") \
     /* capture groups */ \
     SW(heavy_min, u64, 64, "RDFIND_HEAVY_MIN", positive_or(v, s.heavy_min), TEST, \
        "minimum heavy-group size (a power of two; smaller groups are cheaper by binary search than as bit columns)") \

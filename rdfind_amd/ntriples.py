@@ -335,6 +335,60 @@ def _stream_from(files, start):
         base += sz
 
 
+def _stream_all(paths):
+    """read_bytes' stream in pieces of at most _GZ_STEP bytes: every file read (a .gz one decompressed) as it comes,
+    and a line break after a file without a final one."""
+    for path in paths:
+        path = _plain_path(path)
+        opener = gzip.open if path.endswith(".gz") else open
+        last = b"\n"
+        with opener(path, "rb") as f:
+            while chunk := f.read(_GZ_STEP):
+                yield chunk
+                last = chunk[-1:]
+        if last != b"\n":
+            yield b"\n"
+
+
+def iter_windows(paths, window_bytes: int):
+    """The byte stream of :func:`read_bytes` as windows for the chunked device parse (rdf_parse_chunk): each item is
+    the longest run of whole lines that fits in ``window_bytes``, or one line alone if that line is longer.  Every
+    item ends in a line break and their concatenation is ``read_bytes(paths)``.  The files are streamed, so the host
+    holds one window plus one read step at a time (the reference's input splits never hold the text either,
+    FLK/persistence/MultiFileTextInputFormat.java:49-100)."""
+    w = max(int(window_bytes), 1)
+    buf = bytearray()
+    pos = 0   # buf[pos:] is not yet handed out
+    scan = 0  # a first line longer than the window: no line break in buf[pos:scan]
+
+    def take(final):
+        nonlocal pos, scan
+        while pos < len(buf):
+            avail = len(buf) - pos
+            if avail <= w:
+                if not final:
+                    return  # later lines may still fit
+                cut = len(buf)
+            else:
+                cut = buf.rfind(b"\n", pos, pos + w) + 1
+                if cut == 0:  # the first line alone exceeds the window: it goes out whole
+                    cut = buf.find(b"\n", max(scan, pos + w)) + 1
+                    if cut == 0:
+                        scan = len(buf)
+                        return
+            yield bytes(buf[pos:cut])
+            pos, scan = cut, 0
+
+    for chunk in _stream_all(paths):
+        if pos:
+            del buf[:pos]
+            scan = max(scan - pos, 0)
+            pos = 0
+        buf += chunk
+        yield from take(False)
+    yield from take(True)
+
+
 def read_byte_range(paths, rank: int, nranks: int) -> bytes:
     """This rank's part of the input for the sharded ingest: the bytes of the whole lines that start in
     [T * rank / nranks, T * (rank + 1) / nranks) of the concatenated input of T bytes (read_bytes' stream: a line

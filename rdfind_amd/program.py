@@ -12,6 +12,7 @@ this build raise ``NotImplementedError`` instead of silently producing a differe
 from __future__ import annotations
 
 import argparse
+import itertools
 import os
 import sys
 import time
@@ -65,6 +66,9 @@ def build_parser():
                     help="build-specific: discover the CINDs in pages of this much device working memory (0: "
                          "automatic), each page written before the next.  Without it a result larger than the device "
                          "memory switches to pages by itself")
+    ap.add_argument("--ingest-window", type=int, default=1 << 30, metavar="BYTES",
+                    help="build-specific: an input larger than this is parsed on the device in windows of whole lines "
+                         "of at most this many bytes, so neither the host nor the GPU holds the whole text")
     ap.add_argument("--device", type=int, default=0)
     for flag, typ in _RESULT_NEUTRAL.items():
         if typ is None:
@@ -145,8 +149,18 @@ class RDFind:
                 s, p, o, dic = ntriples.read_triples(paths, tabs=a.tabs)
                 n_in = s.shape[0]
                 ctx.set_triples(s, p, o, dic.size)
-            else:  # Parse triples on the device (rdf_parse_ntriples): the host only reads the bytes
-                n_in, _, _ = ctx.parse_ntriples(ntriples.read_bytes(paths), tabs=a.tabs)
+            else:  # Parse triples on the device: the host only reads the bytes.  An input of one window goes in one
+                # call (rdf_parse_ntriples), a larger one window by window (rdf_parse_begin / _chunk / _end)
+                windows = ntriples.iter_windows(paths, a.ingest_window)
+                head = list(itertools.islice(windows, 2))
+                if len(head) < 2:
+                    n_in, _, _ = ctx.parse_ntriples(head[0] if head else b"", tabs=a.tabs)
+                else:
+                    def handed_on():  # one by one, so that no window outlives its parse
+                        while head:
+                            yield head.pop(0)
+                        yield from windows
+                    n_in, _, _ = ctx.parse_windows(handed_on(), tabs=a.tabs)
                 dic = None  # device dictionary, fetched when needed
             if a.prefixes:  # Shorten URLs (RDFind.scala:243-267), once per distinct term
                 if dic is None:
