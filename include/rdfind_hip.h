@@ -185,6 +185,36 @@ rdf_status rdf_parse_end(rdf_ctx* ctx, rdf_parse_stats* stats /* may be null */)
  * (call with cap = 0 to learn it).  RDF_ERR_STATE unless the resident dictionary comes from rdf_parse_end. */
 rdf_status rdf_copy_term_heap(rdf_ctx* ctx, char* out, uint64_t cap, uint64_t* bytes);
 
+/* --asciify-triples and --prefixes on the dictionary of the last device parse (single call or chunked), once per
+ * distinct term and without a host round trip (ALG/programs/RDFind.scala:239-267).  Every term t becomes
+ * shorten(asciify(t)):
+ *   asciify (RDF_RW_ASCIIFY; AsciifyTriples.scala:17-37): each UTF-16 code unit c of the term (a code point
+ *     >= U+10000 is its two surrogates) becomes the bytes c & 0x7F, c >>= 7, ... until c == 0, at least one byte.
+ *     ASCII passes through; the result is pure ASCII and may hold NUL, '\n' and other control bytes.
+ *   shorten (ShortenUrls.scala:36-44): only a term whose last byte is '>' changes; the longest key that is a byte
+ *     prefix of it wins (StringTrie.getKeyAndValue) and the term becomes value + term[len(key) : len(term) - 1].
+ * Keys and values are what ShortenUrls.PrefixTrieCreator puts into its trie: key "<url", value "prefix:"; key i is
+ * key_heap[key_off[i], key_off[i + 1]), value i likewise.  n_keys == 0: only the flag acts.
+ * Terms whose new bytes are equal share one id afterwards; the new ids ascend with the smallest old id of each class
+ * (the ids a dictionary encoding of the rewritten triples assigns); s / p / o are remapped in place, n stays.
+ * Afterwards the context is as rdf_parse_end leaves it: the distinct new terms in the term heap (rdf_copy_terms,
+ * rdf_copy_term_heap, rdf_set_dictionary_parsed), the parsed text of a single-call parse released, the "triples set"
+ * stage.  The call may be repeated.
+ * All or nothing: a failed call leaves triples and dictionary as they were.  RDF_ERR_ARG: a duplicate or empty key
+ * ("Key already exists", StringTrie.scala:37-39); a key that equals a whole term (the JVM's substring exception),
+ * naming the term id; with RDF_RW_ASCIIFY a term that is not valid UTF-8, naming the term id.  RDF_ERR_STATE: the
+ * resident dictionary is not from a device parse, a chunked parse is open, or the input came from the sharded ingest. */
+#define RDF_RW_ASCIIFY 1u
+typedef struct {
+    uint64_t n_terms_before, n_terms_after;  /* after < before when rewritten terms coincide */
+    uint64_t n_changed;                      /* terms a key matched or, asciified, with a non-ASCII character */
+    uint64_t heap_bytes;                     /* bytes of the new term heap (distinct terms only) */
+    float ms;
+} rdf_rewrite_stats;
+rdf_status rdf_rewrite_terms(rdf_ctx* ctx, uint32_t flags, const char* key_heap, const uint64_t* key_off,
+                             const char* val_heap, const uint64_t* val_off, uint32_t n_keys,
+                             rdf_rewrite_stats* stats /* may be null */);
+
 /* Copies min(cap, n) resident triples to host arrays (e.g. after rdf_distinct_triples). */
 rdf_status rdf_copy_triples(rdf_ctx* ctx, uint32_t* s, uint32_t* p, uint32_t* o, uint64_t cap, uint64_t* n_copied);
 

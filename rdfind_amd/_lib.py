@@ -36,11 +36,15 @@ EXPORTED_SYMBOLS = (
     "rdf_dictionary_terms", "rdf_copy_result_refs", "rdf_release_scratch", "rdf_set_handover",
     "rdf_copy_result_refs_async", "rdf_handover_wait", "rdf_set_result_form", "rdf_heavy_chunk_count",
     "rdf_copy_result_heavy", "rdf_parse_begin", "rdf_parse_chunk", "rdf_parse_end", "rdf_copy_term_heap",
+    "rdf_rewrite_terms",
 )
+RDF_RW_ASCIIFY = 1
 RDF_NT_TABS = 1
 
 # the test-only entry points of rdfind_amd/csrc/test_abi.h (not part of the product ABI)
-TEST_SYMBOLS = ("rdf_test_scan", "rdf_test_scan_batch", "rdf_test_radix", "rdf_test_radix_passes", "rdf_test_paths")
+TEST_SYMBOLS = ("rdf_test_scan", "rdf_test_scan_batch", "rdf_test_radix", "rdf_test_radix_passes", "rdf_test_paths",
+                "rdf_test_rewrite_form")
+REWRITE_FORMS = {0: None, 1: "lds", 2: "global"}
 SCAN_U32_U32, SCAN_U32_U64, SCAN_U64_U64 = range(3)
 SCAN_DTYPES = {SCAN_U32_U32: (np.uint32, np.uint32), SCAN_U32_U64: (np.uint32, np.uint64),
                SCAN_U64_U64: (np.uint64, np.uint64)}
@@ -69,6 +73,12 @@ class ParseStats(ctypes.Structure):
     _fields_ = [("n_triples", ctypes.c_uint64), ("n_terms", ctypes.c_uint64), ("n_lines", ctypes.c_uint64),
                 ("n_chunks", ctypes.c_uint64), ("heap_bytes", ctypes.c_uint64), ("table_slots", ctypes.c_uint64),
                 ("n_table_growths", ctypes.c_uint64), ("ms", ctypes.c_float)]
+
+
+class RewriteStats(ctypes.Structure):
+    """rdf_rewrite_stats (rdf_rewrite_terms)."""
+    _fields_ = [("n_terms_before", ctypes.c_uint64), ("n_terms_after", ctypes.c_uint64), ("n_changed", ctypes.c_uint64),
+                ("heap_bytes", ctypes.c_uint64), ("ms", ctypes.c_float)]
 
 
 class GroupStats(ctypes.Structure):
@@ -172,6 +182,7 @@ def load():
         "rdf_parse_chunk": (i32, [P, ctypes.c_char_p, u64, ctypes.POINTER(u64), ctypes.POINTER(u32)]),
         "rdf_parse_end": (i32, [P, ctypes.POINTER(ParseStats)]),
         "rdf_copy_term_heap": (i32, [P, P, u64, ctypes.POINTER(u64)]),
+        "rdf_rewrite_terms": (i32, [P, u32, ctypes.c_char_p, P, ctypes.c_char_p, P, u32, ctypes.POINTER(RewriteStats)]),
         "rdf_frequent_conditions": (i32, [P, u32, ctypes.POINTER(FcStats)]),
         "rdf_build_capture_groups": (i32, [P, ctypes.c_char_p, ctypes.POINTER(GroupStats)]),
         "rdf_discover_cinds": (i32, [P, u32, ctypes.POINTER(CindStats)]),
@@ -228,6 +239,7 @@ def load():
                                  ctypes.POINTER(u32)]),
         "rdf_test_radix_passes": (ctypes.c_int, [ctypes.c_int]),
         "rdf_test_paths": (i32, [P, ctypes.POINTER(PathReport)]),
+        "rdf_test_rewrite_form": (i32, [P, ctypes.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None) if name in TEST_SYMBOLS else getattr(lib, name)
@@ -393,6 +405,31 @@ class Context:
         pos = np.arange(int(offsets[-1]), dtype=np.int64) + np.repeat(off.astype(np.int64) - offsets[:-1].astype(np.int64),
                                                                        ln64)
         return src[pos].tobytes(), offsets
+
+    def rewrite_terms(self, prefixes=(), asciify: bool = False) -> dict:
+        """--asciify-triples and/or --prefixes on the device dictionary of the last parse (rdf_rewrite_terms): every
+        distinct term becomes shorten(asciify(term)), equal results share one id, and s / p / o are remapped in HBM.
+        ``prefixes`` is [(prefix, url)] as ``ntriples.read_prefixes`` returns it; the keys ``<url`` and the values
+        ``prefix:`` are formed here (ShortenUrls.PrefixTrieCreator).  Returns the stats (n_terms_before, n_terms_after,
+        n_changed, heap_bytes, ms); :meth:`parsed_terms` fetches the new dictionary afterwards."""
+        keys = [("<" + url).encode("utf-8") for _, url in prefixes]
+        vals = [(prefix + ":").encode("utf-8") for prefix, _ in prefixes]
+        koff, voff = np.zeros(len(keys) + 1, np.uint64), np.zeros(len(keys) + 1, np.uint64)
+        np.cumsum([len(k) for k in keys], out=koff[1:])
+        np.cumsum([len(v) for v in vals], out=voff[1:])
+        st = RewriteStats()
+        self._check(self.lib.rdf_rewrite_terms(self.ptr, RDF_RW_ASCIIFY if asciify else 0, b"".join(keys), koff.ctypes.data,
+                                               b"".join(vals), voff.ctypes.data, len(keys), ctypes.byref(st)),
+                    "rdf_rewrite_terms")
+        self.num_terms = int(st.n_terms_after)
+        self._parsed = None  # the new term heap, fetched when parsed_terms asks for it
+        return {k: (float(st.ms) if k == "ms" else int(getattr(st, k))) for k, _ in RewriteStats._fields_}
+
+    def rewrite_form(self):
+        """Which key lookup the last :meth:`rewrite_terms` ran (rdf_test_rewrite_form): "lds", "global" or None."""
+        v = ctypes.c_uint32()
+        self._check(self._test_fn("rdf_test_rewrite_form")(self.ptr, ctypes.byref(v)), "rdf_test_rewrite_form")
+        return REWRITE_FORMS[int(v.value)]
 
     def set_dictionary_parsed(self):
         """The last parse's dictionary becomes the formatting dictionary, in HBM (rdf_set_dictionary_parsed)."""

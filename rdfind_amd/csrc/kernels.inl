@@ -4248,6 +4248,8 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_nt_assign_chunk(const u32* __rest
     }
 }
 
+#include "rewrite.inl"
+
 }  // namespace rdf
 
 namespace rdf {

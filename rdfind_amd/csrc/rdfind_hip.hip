@@ -51,6 +51,10 @@ using namespace rdf;
     /* offsets and text positions */ \
     B(INPUT, ntheap) B(INPUT, nthash) B(INPUT, nptab) \
     B(PARSE, nwin) B(PARSE, ngid) B(PARSE, nmiss) B(PARSE, nnlen) B(PARSE, nnoff) B(PARSE, nsrc) \
+    /* rdf_rewrite_terms (rewrite.inl), all scratch of the call: the key tables, each term's matched key, the rewritten */ \
+    /* terms' bytes before the re-deduplication, old id -> new id; the new term table and heap, which change places */ \
+    /* with nterm_off / nterm_len / ntheap once they are complete (the old ones are then released as scratch) */ \
+    B(PARSE, rwkeys) B(PARSE, rwkm) B(PARSE, rwheap) B(PARSE, rwmap) B(PARSE, rwtoff) B(PARSE, rwtlen) B(PARSE, rwnheap) \
     /* frequent conditions */ \
     B(RUN, frank) B(RUN, fval) B(RUN, fext) \
     B(RUN, cnt) B(SPARE_FC, tkeys) B(RUN, tcnt) B(RUN, bkeys) B(RUN, bkeys_tmp) B(RUN, lkeys) B(RUN, lvals) B(RUN, flags) \
@@ -176,6 +180,7 @@ struct rdf_ctx : CtxBuffers {
     bool dict_in_heap = false;  // nterm_off points into ntheap (chunked parse), not into ntext
     // chunked parse (rdf_parse_begin .. rdf_parse_end): totals so far
     bool parse_open = false;
+    u32 rw_form = 0;  // the key lookup of the last rdf_rewrite_terms (RDF_TEST_RW_*; 0: none ran, or it had no keys)
     u32 parse_flags = 0;
     u64 pc_n = 0, pc_V = 0, pc_lines = 0, pc_chunks = 0, pc_heap = 0, pc_slots = 0, pc_growths = 0;
     float pc_ms = 0;
@@ -1206,6 +1211,213 @@ rdf_status rdf_copy_term_heap(rdf_ctx* c, char* out, uint64_t cap, uint64_t* byt
     HIP_TRY(c, hipSetDevice(c->device));
     if (n) HIP_TRY(c, ctx_copy(c, out, c->ntheap.p, n, hipMemcpyDeviceToHost));
     if (bytes) *bytes = c->pc_heap;
+    return RDF_OK;
+}
+
+// --asciify-triples / --prefixes on the device dictionary (rewrite.inl).  Nothing resident is written before every
+// buffer of the result exists and the error flags have been read: the remap of s / p / o and the exchange of the term
+// table come last.
+static rdf_status rewrite_body(rdf_ctx* c, u32 flags, const char* key_heap, const uint64_t* key_off, const char* val_heap,
+                               const uint64_t* val_off, u32 nk, rdf_rewrite_stats* stats) {
+    hipStream_t st = c->stream;
+    const bool asc = (flags & RDF_RW_ASCIIFY) != 0;
+    const u64 V = c->n_terms_parsed;
+    // the key tables, built here and uploaded in one piece:
+    // th[slots] u64 | tk[slots] u32 | koff[nk + 1] | voff[nk + 1] | vlen[nk] | lenbits | key bytes | value bytes
+    const u64 kbytes = nk ? key_off[nk] - key_off[0] : 0, vbytes = nk ? val_off[nk] - val_off[0] : 0;
+    if (kbytes >= (1ull << 31) || vbytes >= (1ull << 31)) return fail(c, RDF_ERR_LIMIT, "the prefix table must be < 2^31 bytes");
+    u32 maxlen = 0;
+    for (u32 k = 0; k < nk; ++k) {
+        if (key_off[k + 1] <= key_off[k]) return fail(c, RDF_ERR_ARG, "empty key " + std::to_string(k));
+        if (val_off[k + 1] < val_off[k]) return fail(c, RDF_ERR_ARG, "value offsets must ascend");
+        maxlen = std::max<u32>(maxlen, (u32)(key_off[k + 1] - key_off[k]));
+    }
+    const u32 slots = (u32)next_pow2(std::max<u64>(2ull * nk, 2)), nbits = maxlen / 32 + 1;
+    auto al8 = [](u64 x) { return (x + 7) & ~7ull; };
+    const u64 o_th = 0, o_tk = o_th + 8ull * slots, o_koff = al8(o_tk + 4ull * slots), o_voff = al8(o_koff + 4ull * (nk + 1)),
+              o_vlen = al8(o_voff + 4ull * (nk + 1)), o_bits = al8(o_vlen + 4ull * nk), o_kh = al8(o_bits + 4ull * nbits),
+              o_vh = al8(o_kh + kbytes + 4), total_k = al8(o_vh + vbytes + 4);
+    std::vector<unsigned char> hk(total_k, 0);
+    u64* th = (u64*)(hk.data() + o_th);
+    u32 *tk = (u32*)(hk.data() + o_tk), *koff = (u32*)(hk.data() + o_koff), *voff = (u32*)(hk.data() + o_voff),
+        *vlen = (u32*)(hk.data() + o_vlen), *bits = (u32*)(hk.data() + o_bits);
+    for (u32 i = 0; i < slots; ++i) tk[i] = RW_NONE;
+    if (nk) {
+        memcpy(hk.data() + o_kh, key_heap + key_off[0], kbytes);
+        memcpy(hk.data() + o_vh, val_heap + val_off[0], vbytes);
+    }
+    for (u32 k = 0; k <= nk && nk; ++k) {
+        koff[k] = (u32)(key_off[k] - key_off[0]);
+        voff[k] = (u32)(val_off[k] - val_off[0]);
+    }
+    for (u32 k = 0; k < nk; ++k) {
+        const unsigned char* kb = hk.data() + o_kh + koff[k];
+        const u32 L = koff[k + 1] - koff[k];
+        vlen[k] = voff[k + 1] - voff[k];
+        bits[L >> 5] |= 1u << (L & 31);
+        u64 h = rw_hash0();
+        for (u32 i = 0; i < L; ++i) h = rw_hash_step(h, kb[i]);
+        u32 sl = rw_slot(h, slots - 1);
+        for (; tk[sl] != RW_NONE; sl = (sl + 1) & (slots - 1)) {  // (load <= 1/2: an empty slot ends the walk)
+            const u32 j = tk[sl];
+            if (th[sl] == h && koff[j + 1] - koff[j] == L && !memcmp(hk.data() + o_kh + koff[j], kb, L))
+                return fail(c, RDF_ERR_ARG, "Key already exists: " + std::string((const char*)kb, L) + ".");  // StringTrie.+=
+        }
+        th[sl] = h;
+        tk[sl] = k;
+    }
+    c->rw_form = 0;
+    if (!V) {  // no terms: only the state changes (the dictionary lies in the heap afterwards)
+        ENSURE(c, rwnheap, 16);
+        HIP_TRY(c, hipMemsetAsync(c->rwnheap.p, 0, 16, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        std::swap(c->ntheap, c->rwnheap);
+        c->pc_heap = 0;
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RDF_OK;
+    }
+    const unsigned char* src = (const unsigned char*)(c->dict_in_heap ? c->ntheap.p : c->ntext.p);
+    ENSURE(c, rwkeys, total_k);
+    HIP_TRY(c, hipMemcpyAsync(c->rwkeys.p, hk.data(), total_k, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->ev[6], st));
+    const unsigned char* dk = (const unsigned char*)c->rwkeys.p;
+    RwKeys K;
+    K.th = (const u64*)(dk + o_th);
+    K.tk = (const u32*)(dk + o_tk);
+    K.koff = (const u32*)(dk + o_koff);
+    K.lenbits = (const u32*)(dk + o_bits);
+    K.kheap = dk + o_kh;
+    K.mask = slots - 1;
+    K.maxlen = maxlen;
+    K.n_keys = nk;
+    K.kbytes = (u32)kbytes;
+    const u32 *d_voff = (const u32*)(dk + o_voff), *d_vlen = (const u32*)(dk + o_vlen);
+    const bool lds = nk && slots <= RW_LDS_SLOTS && kbytes <= RW_LDS_HEAP && maxlen <= RW_LDS_MAXLEN;
+    c->rw_form = !nk ? 0 : lds ? RDF_TEST_RW_LDS : RDF_TEST_RW_GLOBAL;
+    // lengths and error flags
+    ENSURE(c, ntlen, V * 4);
+    ENSURE(c, rwkm, V * 4);
+    ENSURE(c, ntstart, (V + 1) * 8);
+    HIP_TRY(c, hipMemsetAsync(dscal(c, 1), 0xff, 3 * 8, st));
+    HIP_TRY(c, hipMemsetAsync(dscal(c, 4), 0, 8, st));
+    const unsigned gv = grid_for(V, RDF_BLOCK, kGrid);
+    const u64* toff = c->nterm_off.as<u64>();
+    const u32* tlen = c->nterm_len.as<u32>();
+    u32 *nlen = c->ntlen.as<u32>(), *km = c->rwkm.as<u32>();
+#define RW_LEN(ASC, LDS) \
+    hipLaunchKernelGGL((k_rw_len<ASC, LDS>), dim3(gv), dim3(RDF_BLOCK), 0, st, src, toff, tlen, V, K, d_vlen, nlen, km, dscal(c, 1))
+    if (asc && lds) RW_LEN(true, true);
+    else if (asc) RW_LEN(true, false);
+    else if (lds) RW_LEN(false, true);
+    else RW_LEN(false, false);
+#undef RW_LEN
+    u64* noff = c->ntstart.as<u64>();
+    HIP_TRY(c, exclusive_scan_u32_u64(c->ws, nlen, noff, V, dscal(c, 0), st));
+    u64 sc[5];
+    TRY(read_multi(c, {{dscal(c, 0), 8}, {dscal(c, 1), 8}, {dscal(c, 2), 8}, {dscal(c, 3), 8}, {dscal(c, 4), 8}}, sc));
+    if (sc[2] != ~0ull) return fail(c, RDF_ERR_ARG, "term " + std::to_string(sc[2]) + " is not valid UTF-8 (RDF_RW_ASCIIFY)");
+    if (sc[1] != ~0ull) return fail(c, RDF_ERR_ARG, "a prefix key covers the whole of term " + std::to_string(sc[1]));
+    if (sc[3] != ~0ull) return fail(c, RDF_ERR_LIMIT, "term " + std::to_string(sc[3]) + " would exceed 2^32 bytes");
+    const u64 raw_bytes = sc[0], n_changed = sc[4];
+    // the new bytes and their hashes
+    ENSURE(c, rwheap, raw_bytes + 16);
+    ENSURE(c, nhv, V * 8);
+    HIP_TRY(c, hipMemsetAsync((char*)c->rwheap.p + (raw_bytes & ~3ull), 0, 16 + raw_bytes - (raw_bytes & ~3ull), st));
+    const unsigned gw = grid_for(V, RDF_WAVE * RDF_WAVES_PER_BLOCK, kGrid);
+    unsigned char* raw = (unsigned char*)c->rwheap.p;
+    if (asc)
+        hipLaunchKernelGGL(k_rw_write<true>, dim3(gw), dim3(RDF_BLOCK), 0, st, src, toff, tlen, V, K.koff, d_voff, dk + o_vh,
+                           km, nlen, noff, raw);
+    else
+        hipLaunchKernelGGL(k_rw_write<false>, dim3(gw), dim3(RDF_BLOCK), 0, st, src, toff, tlen, V, K.koff, d_voff, dk + o_vh,
+                           km, nlen, noff, raw);
+    hipLaunchKernelGGL(k_rw_hash, dim3(gv), dim3(RDF_BLOCK), 0, st, raw, noff, nlen, V, c->nhv.as<u64>());
+    // equal new terms: the first-occurrence table over the old ids
+    const u64 T = next_pow2(2 * V);
+    ENSURE(c, ntab, T * 8);
+    ENSURE(c, nvalid, V * 4);
+    ENSURE(c, nslot, V * 4);
+    ENSURE(c, nrep, V * 4);
+    ENSURE(c, nfirst, V * 4);
+    ENSURE(c, nfid, V * 4);
+    ENSURE(c, nnlen, V * 4);
+    ENSURE(c, nnoff, V * 8);
+    HIP_TRY(c, hipMemsetAsync(c->ntab.p, 0xff, T * 8, st));
+    HIP_TRY(c, hipMemsetAsync(c->nvalid.p, 0xff, V * 4, st));
+    hipLaunchKernelGGL(k_nt_dict_insert<1>, dim3(gv), dim3(RDF_BLOCK), 0, st, raw, noff, nlen, c->nvalid.as<u32>(), V,
+                       c->nhv.as<u64>(), c->ntab.as<u64>(), T - 1, c->nslot.as<u32>(), nt_fp_mask(32));
+    hipLaunchKernelGGL(k_nt_dict_rep<1>, dim3(gv), dim3(RDF_BLOCK), 0, st, c->nvalid.as<u32>(), V, c->nslot.as<u32>(),
+                       c->ntab.as<u64>(), c->nrep.as<u32>(), c->nfirst.as<u32>());
+    HIP_TRY(c, hipMemsetAsync(dscal(c, 3), 0, 8, st));
+    HIP_TRY(c, exclusive_scan_u32(c->ws, c->nfirst.as<u32>(), c->nfid.as<u32>(), V, (u32*)dscal(c, 3), st));
+    hipLaunchKernelGGL(k_nt_new_len, dim3(gv), dim3(RDF_BLOCK), 0, st, c->nfirst.as<u32>(), nlen, V, c->nnlen.as<u32>());
+    HIP_TRY(c, exclusive_scan_u32_u64(c->ws, c->nnlen.as<u32>(), c->nnoff.as<u64>(), V, dscal(c, 4), st));
+    TRY(read_multi(c, {{dscal(c, 3), 8}, {dscal(c, 4), 8}}, sc));
+    const u64 V1 = sc[0], heap1 = sc[1];
+    // the new term table and heap; old id -> new id
+    ENSURE(c, rwmap, V * 4);
+    ENSURE(c, rwtoff, V1 * 8);
+    ENSURE(c, rwtlen, V1 * 4);
+    ENSURE(c, nsrc, V1 * 8);
+    ENSURE(c, rwnheap, heap1 + 16);
+    HIP_TRY(c, hipMemsetAsync((char*)c->rwnheap.p + (heap1 & ~3ull), 0, 16 + heap1 - (heap1 & ~3ull), st));
+    hipLaunchKernelGGL(k_rw_compact, dim3(gv), dim3(RDF_BLOCK), 0, st, c->nrep.as<u32>(), c->nfirst.as<u32>(),
+                       c->nfid.as<u32>(), noff, nlen, c->nnoff.as<u64>(), V, c->rwmap.as<u32>(), c->rwtoff.as<u64>(),
+                       c->rwtlen.as<u32>(), c->nsrc.as<u64>());
+    const u64 words = (heap1 + 3) >> 2;
+    if (words)
+        hipLaunchKernelGGL(k_nt_append_bytes, dim3(grid_for(words, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, raw,
+                           c->nsrc.as<u64>(), c->rwtoff.as<u64>(), V1, 0ull, heap1, c->rwnheap.as<u32>());
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));  // everything above has run without an error: the resident state changes now
+    if (c->n)
+        hipLaunchKernelGGL(k_rw_remap, dim3(grid_for(c->n / 4 + 1, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st,
+                           c->ts.as<u32>(), c->tp.as<u32>(), c->to.as<u32>(), c->n, c->rwmap.as<u32>());
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev[7], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    std::swap(c->nterm_off, c->rwtoff);
+    std::swap(c->nterm_len, c->rwtlen);
+    std::swap(c->ntheap, c->rwnheap);
+    c->n_terms_parsed = V1;
+    c->V = (u32)V1;
+    c->pc_heap = heap1;
+    if (stats) {
+        stats->n_terms_before = V;
+        stats->n_terms_after = V1;
+        stats->n_changed = n_changed;
+        stats->heap_bytes = heap1;
+        HIP_TRY(c, hipEventElapsedTime(&stats->ms, c->ev[6], c->ev[7]));
+    }
+    return RDF_OK;
+}
+
+rdf_status rdf_rewrite_terms(rdf_ctx* c, uint32_t flags, const char* key_heap, const uint64_t* key_off, const char* val_heap,
+                             const uint64_t* val_off, uint32_t n_keys, rdf_rewrite_stats* stats) {
+    if (!c) return RDF_ERR_ARG;
+    if (n_keys && (!key_heap || !key_off || !val_heap || !val_off)) return fail(c, RDF_ERR_ARG, "null key table");
+    if (flags & ~RDF_RW_ASCIIFY) return fail(c, RDF_ERR_ARG, "unknown rewrite flags");
+    if (c->parse_open) return fail(c, RDF_ERR_STATE, "a chunked parse is open (rdf_parse_end comes first)");
+    if (c->ingest_sharded) return fail(c, RDF_ERR_STATE, "terms of a sharded ingest cannot be rewritten");
+    if (!c->parsed_dict || c->stage < 1)
+        return fail(c, RDF_ERR_STATE, "the resident dictionary does not come from a device parse");
+    HIP_TRY(c, hipSetDevice(c->device));
+    TRY(hv_wait(c, true));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const rdf_status rs = rewrite_body(c, flags, key_heap, key_off, val_heap, val_off, n_keys, stats);
+    // the call's scratch, on success the old term table and heap among it
+    for_each_buf(c, [](DevBuf& b, const BufEntry& e) {
+        if (e.cls == BUF_PARSE) b.release();
+    });
+    (void)hipGetLastError();
+    if (rs) return rs;
+    c->ntext.release();  // a single-call parse's text: the terms lie in the heap now
+    c->dict_in_heap = c->parsed_dict = true;
+    c->s = c->ts.as<u32>();
+    c->p = c->tp.as<u32>();
+    c->o = c->to.as<u32>();
+    c->stage = 1;
+    c->paged = false;
     return RDF_OK;
 }
 

@@ -74,6 +74,11 @@ typedef struct rdf_test_path_report {
 
 rdf_status rdf_test_paths(rdf_ctx* ctx, rdf_test_path_report* out);
 
+/* The key lookup of the last rdf_rewrite_terms: the tables staged in LDS, or read from global memory (a table too
+ * large for LDS).  0: no call yet, or the last one had no keys or no terms. */
+enum { RDF_TEST_RW_LDS = 1, RDF_TEST_RW_GLOBAL = 2 };
+rdf_status rdf_test_rewrite_form(rdf_ctx* ctx, uint32_t* form);
+
 #ifdef __cplusplus
 }
 #endif

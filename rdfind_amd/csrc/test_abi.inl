@@ -195,4 +195,10 @@ rdf_status rdf_test_paths(rdf_ctx* c, rdf_test_path_report* out) {
     return RDF_OK;
 }
 
+rdf_status rdf_test_rewrite_form(rdf_ctx* c, uint32_t* form) {
+    if (!c || !form) return RDF_ERR_ARG;
+    *form = c->rw_form;
+    return RDF_OK;
+}
+
 }  // extern "C"

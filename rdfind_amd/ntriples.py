@@ -251,13 +251,34 @@ class PrefixTable:
         return term
 
 
-def shorten_dictionary(s, p, o, dictionary: Dictionary, prefixes):
+def asciify(term: str) -> str:
+    """AsciifyTriples.asciify (ALG/operators/AsciifyTriples.scala:17-37), restated literally: for every ``char`` of
+    the string (a UTF-16 code unit, so a code point >= U+10000 is its two surrogates) ``do { sb.append((c & 0x7F)
+    .toChar); c >>= 7 } while (c != 0)``.  ASCII characters pass through; the result is pure ASCII."""
+    if term.isascii():
+        return term
+    sb = []
+    units = term.encode("utf-16-le", "surrogatepass")
+    for i in range(0, len(units), 2):
+        c = units[i] | (units[i + 1] << 8)
+        while True:
+            sb.append(chr(c & 0x7F))
+            c >>= 7
+            if c == 0:
+                break
+    return "".join(sb)
+
+
+def shorten_dictionary(s, p, o, dictionary: Dictionary, prefixes, asciify_terms: bool = False):
     """Applies the URL shortening to every distinct term once (not to every triple, as the reference's
     per-triple map does) and re-encodes: terms that shorten to the same string share one id afterwards,
-    exactly as they would have after a per-triple map followed by dictionary encoding."""
+    exactly as they would have after a per-triple map followed by dictionary encoding.
+    ``asciify_terms``: --asciify-triples, which the reference's plan applies directly before the shortening
+    (RDFind.scala:239-241): every distinct term becomes shorten(asciify(term))."""
     table = PrefixTable(prefixes)
     short = Dictionary()
-    remap = np.fromiter((short.encode(table.shorten(t)) for t in dictionary.terms), dtype=np.uint32,
+    rewrite = (lambda t: table.shorten(asciify(t))) if asciify_terms else table.shorten
+    remap = np.fromiter((short.encode(rewrite(t)) for t in dictionary.terms), dtype=np.uint32,
                         count=dictionary.size)
     return remap[s], remap[p], remap[o], short
 

@@ -1,9 +1,11 @@
 """RDFind-compatible driver: same flags, same plan stages, same ``Cind.toString`` output.
 
 Mirrors ``RDFind.createFlinkPlan`` (ALG/programs/RDFind.scala:196-580) for the hot path:
-read + parse N-Triples -> (optional) distinct triples -> frequent conditions (--use-fis) -> capture
-groups -> traversal strategy (0 AllAtOnce, 1 S2L) incl. --clean-implied -> output.  The three middle
-stages run on the GPU through the C ABI (``include/rdfind_hip.h``); there is no CPU fallback.
+read + parse N-Triples -> (optional) asciify / shorten URLs -> (optional) distinct triples -> frequent conditions
+(--use-fis) -> capture groups -> traversal strategy (0 AllAtOnce, 1 S2L) incl. --clean-implied -> output.  The parse,
+the term rewrite (--asciify-triples, --prefixes: one ``rdf_rewrite_terms`` over the device dictionary) and the three
+middle stages run on the GPU through the C ABI (``include/rdfind_hip.h``); there is no CPU fallback.  With
+``--host-parser`` the parse and the term rewrite run on the host instead (rdfind_amd/ntriples.py, same results).
 
 Flag names follow ``RDFind.Parameters`` (RDFind.scala:639-721).  Flags that only change how Flink
 executes (and not the result) are accepted and ignored; flags whose semantics are out of scope for
@@ -33,7 +35,7 @@ _RESULT_NEUTRAL = {
 FORMAT_CHUNK = 1 << 23     # result rows formatted per device call
 KEEP_LINES_MAX = 1 << 24   # run() returns the lines as a list up to this many CINDs (None above)
 
-_UNSUPPORTED = ["--asciify-triples", "--apply-hash", "--hash-dictionary",
+_UNSUPPORTED = ["--apply-hash", "--hash-dictionary",
                 "--hash-function", "--hash-bytes", "--any-binary-captures", "--find-frequent-captures",
                 "--explicit-threshold", "--sbf-bytes", "--balanced-overlap-candidates"]
 
@@ -55,6 +57,8 @@ def build_parser():
                     help="parse and dictionary-encode on the host instead of the device (same rules and ids)")
     ap.add_argument("--prefixes", action="append", default=None,
                     help="a list of nt-prefix files to apply on the input triple (repeatable or comma-separated)")
+    ap.add_argument("--asciify-triples", action="store_true",
+                    help="whether to replace non-ASCII characters in the triples (before the prefixes)")
     ap.add_argument("--collect-result", action="store_true", help="whether to collect the results locally")
     ap.add_argument("--debug-level", type=int, default=0, help="0: no debug prints, 1: some, ...")
     ap.add_argument("--find-only-fcs", type=int, default=0)
@@ -101,6 +105,7 @@ class RDFind:
             # with --use-fis (RDFind.scala:290-296); without it their broadcast set is null
             raise ValueError("--use-ars / --ar-output require --use-fis")
         self.timings = {}
+        self.rewrite_stats = None  # rdf_rewrite_stats of the device term rewrite (--prefixes / --asciify-triples)
 
     def log(self, msg):
         print(msg, file=sys.stderr)
@@ -142,7 +147,7 @@ class RDFind:
         paths = ntriples.resolve_paths(a.inputs)
         if not paths:
             raise ValueError("no input files")
-        if world > 1 and not (a.host_parser or a.prefixes or a.distinct_triples or a.only_read):
+        if world > 1 and not (a.host_parser or a.prefixes or a.asciify_triples or a.distinct_triples or a.only_read):
             return self.run_sharded_ingest(paths, device, t0, out)
         with _lib.Context(device) as ctx:
             if a.host_parser:  # host tokenizer + dictionary (rdfind_amd/ntriples.py)
@@ -162,13 +167,19 @@ class RDFind:
                         yield from windows
                     n_in, _, _ = ctx.parse_windows(handed_on(), tabs=a.tabs)
                 dic = None  # device dictionary, fetched when needed
-            if a.prefixes:  # Shorten URLs (RDFind.scala:243-267), once per distinct term
+            if a.prefixes or a.asciify_triples:  # Asciify triples, Shorten URLs (RDFind.scala:239-267), once per
+                # distinct term: on the device dictionary (rdf_rewrite_terms), or on the host parser's
+                files = [x for arg in a.prefixes or [] for x in arg.split(",") if x]
+                prefixes = ntriples.read_prefixes(files)
                 if dic is None:
-                    dic = ntriples.HeapDictionary(*ctx.parsed_terms())
-                    s, p, o = ctx.copy_triples(n_in)
-                files = [x for arg in a.prefixes for x in arg.split(",") if x]
-                s, p, o, dic = ntriples.shorten_dictionary(s, p, o, dic, ntriples.read_prefixes(files))
-                ctx.set_triples(s, p, o, dic.size)
+                    rw = ctx.rewrite_terms(prefixes, asciify=a.asciify_triples)
+                    self.rewrite_stats = rw
+                    self.stats = {"rewrite": rw}
+                    if a.debug_level >= 1:
+                        self.log(f"{rw['n_changed']} terms rewritten, {rw['n_terms_before'] - rw['n_terms_after']} merged.")
+                else:
+                    s, p, o, dic = ntriples.shorten_dictionary(s, p, o, dic, prefixes, asciify_terms=a.asciify_triples)
+                    ctx.set_triples(s, p, o, dic.size)
             self.timings["read"] = time.time() - t0
             if a.only_read:
                 return []
@@ -236,7 +247,8 @@ class RDFind:
         """-dop N with the input split over the ranks: each rank parses only its part of the bytes, the global
         dictionary is built by the terms' owner ranks (distributed.run_ingest), the rank keeps only its triples
         (RDF_SHARD_LOCAL_SLICE), and the formatter gets the terms it needs from their owners (run_dictionary).
-        --prefixes, --distinct-triples and --host-parser keep the replicated parse (a shared host dictionary)."""
+        --prefixes, --asciify-triples, --distinct-triples and --host-parser keep the replicated parse: every rank parses
+        the same bytes and rewrites its own device dictionary, which gives the same ids on every rank."""
         from . import distributed
         a = self.args
         with _lib.Context(device) as ctx:
@@ -275,6 +287,8 @@ class RDFind:
         ctx.sync()
         self.timings["discover"] = time.time() - t1
         self.stats = stats
+        if self.rewrite_stats is not None:
+            self.stats["rewrite"] = self.rewrite_stats
         t2 = time.time()
         if dictionary_ready:
             pass  # the sharded ingest's dictionary by owner lookup (distributed.run_dictionary)
