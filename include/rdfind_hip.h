@@ -452,6 +452,53 @@ rdf_status rdf_num_terms(rdf_ctx* ctx, uint32_t* n);
 /* offsets[n + 1]: term ids[i] is out[offsets[i], offsets[i+1]); RDF_ERR_ARG (offsets filled) if cap is too small. */
 rdf_status rdf_dictionary_terms(rdf_ctx* ctx, const uint32_t* ids, uint64_t n, char* out, uint64_t cap, uint64_t* offsets);
 
+/*
+ * Dataset statistics on the device: the numbers a user reads before a discovery run (which --support to pass, how
+ * skewed the join is).  Integer keys, the pipeline's radix sort and run lengths over the resident triples; each call
+ * leaves the stage, the frequent-condition state and every result exactly as they were, and keeps its rows until the
+ * next histogram call (or rdf_release_scratch, or a new input that makes the context drop its per-run buffers).
+ *
+ * Rows are sorted ascending by (kind, value).
+ */
+typedef struct {
+    uint32_t kind;
+    uint32_t value;
+    uint64_t times;
+} rdf_hist_row;
+/* Copies min(cap, rows) rows of the last histogram call; RDF_ERR_STATE without one. */
+rdf_status rdf_copy_histogram(rdf_ctx* ctx, rdf_hist_row* out, uint64_t cap, uint64_t* n_copied);
+
+/* CountConditions (ALG/programs/CountConditions.scala:192-212): every triple counts towards six conditions, s (kind 1),
+ * p (2), o (4), sp (3), so (5), po (6) -- the ConditionCodes values; duplicate triples count.  A row (kind, c, t) says
+ * that t distinct conditions of that kind occur in exactly c triples; kind 0 is the overall histogram: for each c the
+ * sum of t over the six kinds.  Needs only resident triples (any stage from "triples set" on) and allocates nothing
+ * proportional to num_terms, so sparse ids up to 2^30 - 2 work.  *n_rows receives the row count, *ms (optional) the
+ * device time.  Limit: 3 n < 2^32 (the sort primitives' bound), else RDF_ERR_LIMIT. */
+rdf_status rdf_condition_histogram(rdf_ctx* ctx, uint64_t* n_rows, float* ms);
+
+/* --create-join-histogram (ALG/programs/RDFind.scala:449-452): rows (0, k, t) = t join values whose JoinLine holds
+ * exactly k distinct conditions; *n_lines = the sum of t.  A join value that gets no condition has no line (there is
+ * no size 0).  The lines are those of CreateJoinPartners (ALG/operators/CreateJoinPartners.scala:86-147) followed by
+ * UnionJoinCandidates and UnionCombinedJoinCandidates: per triple and projection attribute the binary capture when it
+ * is emitted, else the conditional unary capture, plus the always-emitted unary capture; distinct per join value; no
+ * split components and no support filter on captures (the group CSR of rdf_build_capture_groups differs in both).
+ *   default        needs a completed rdf_frequent_conditions (RDF_ERR_STATE otherwise) and uses its frequent
+ *                  conditions, without the binary conditions that rdf_association_rules found implied if it ran;
+ *                  callable at any later stage too.  Single GPU: RDF_ERR_STATE after a sharded run.
+ *   RDF_JH_NO_FIS  needs only resident triples: every value passes and every binary capture is emitted, exactly two
+ *                  records per triple and projection attribute (the reference without --use-fis).
+ * projection as for rdf_build_capture_groups.  Limit: 6 n < 2^32 records (one sort), else RDF_ERR_LIMIT; join ranges
+ * for larger inputs are out of scope. */
+#define RDF_JH_NO_FIS 1u
+rdf_status rdf_join_histogram(rdf_ctx* ctx, const char* projection, uint32_t flags, uint64_t* n_lines, uint64_t* n_rows,
+                              float* ms);
+
+/* CountDistinctValues (ALG/programs/CountDistinctValues.scala:112-119): the terms of the device dictionary whose first
+ * byte is '"' are the literals, the other n_terms - n_literals the "URLs".  Works after rdf_parse_ntriples,
+ * rdf_parse_end and rdf_rewrite_terms; RDF_ERR_STATE if the resident dictionary is not from a device parse (or is the
+ * distributed one of a sharded ingest). */
+rdf_status rdf_count_literals(rdf_ctx* ctx, uint64_t* n_literals, uint64_t* n_terms);
+
 /* Device time (ms) of the last call of each stage: [0] fc, [1] groups, [2] cinds. */
 rdf_status rdf_stage_times(rdf_ctx* ctx, float* ms3);
 /* Device time (ms) of each kernel family (RDF_T_*) in the last calls; count <= RDF_NUM_TIMERS. */

@@ -36,8 +36,9 @@ EXPORTED_SYMBOLS = (
     "rdf_dictionary_terms", "rdf_copy_result_refs", "rdf_release_scratch", "rdf_set_handover",
     "rdf_copy_result_refs_async", "rdf_handover_wait", "rdf_set_result_form", "rdf_heavy_chunk_count",
     "rdf_copy_result_heavy", "rdf_parse_begin", "rdf_parse_chunk", "rdf_parse_end", "rdf_copy_term_heap",
-    "rdf_rewrite_terms",
+    "rdf_rewrite_terms", "rdf_condition_histogram", "rdf_join_histogram", "rdf_copy_histogram", "rdf_count_literals",
 )
+RDF_JH_NO_FIS = 1
 RDF_RW_ASCIIFY = 1
 RDF_NT_TABS = 1
 
@@ -138,6 +139,8 @@ class ExchangeRequest:
 RULE_DTYPE = np.dtype([("antecedent_type", "<u4"), ("consequent_type", "<u4"), ("antecedent", "<u4"),
                        ("consequent", "<u4"), ("support", "<u4")])
 CIND_DTYPE = np.dtype([("dep", "<u4"), ("ref", "<u4"), ("support", "<u4")])
+# rdf_hist_row (include/rdfind_hip.h): one histogram row, sorted by (kind, value)
+HIST_DTYPE = np.dtype([("kind", "<u4"), ("value", "<u4"), ("times", "<u8")])
 # rdf_cind_row (include/rdfind_hip.h): the reference's Cind shape with term ids
 ROW_DTYPE = np.dtype([("dep_capture_type", "<u4"), ("dep_value1", "<u4"), ("dep_value2", "<u4"),
                       ("ref_capture_type", "<u4"), ("ref_value1", "<u4"), ("ref_value2", "<u4"), ("support", "<u4")])
@@ -183,6 +186,11 @@ def load():
         "rdf_parse_end": (i32, [P, ctypes.POINTER(ParseStats)]),
         "rdf_copy_term_heap": (i32, [P, P, u64, ctypes.POINTER(u64)]),
         "rdf_rewrite_terms": (i32, [P, u32, ctypes.c_char_p, P, ctypes.c_char_p, P, u32, ctypes.POINTER(RewriteStats)]),
+        "rdf_condition_histogram": (i32, [P, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_float)]),
+        "rdf_join_histogram": (i32, [P, ctypes.c_char_p, u32, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                     ctypes.POINTER(ctypes.c_float)]),
+        "rdf_copy_histogram": (i32, [P, P, u64, ctypes.POINTER(u64)]),
+        "rdf_count_literals": (i32, [P, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "rdf_frequent_conditions": (i32, [P, u32, ctypes.POINTER(FcStats)]),
         "rdf_build_capture_groups": (i32, [P, ctypes.c_char_p, ctypes.POINTER(GroupStats)]),
         "rdf_discover_cinds": (i32, [P, u32, ctypes.POINTER(CindStats)]),
@@ -286,6 +294,7 @@ class Context:
         if rc != 0:
             raise RdfError(f"rdf_ctx_create(device={device}) failed ({rc}): is a GPU visible?")
         self.num_terms = 0
+        self.hist_rows = self.join_lines = 0
         self.fc = self.groups = self.cinds = None
 
     def close(self):
@@ -449,6 +458,44 @@ class Context:
         self._check(self.lib.rdf_copy_triples(self.ptr, s.ctypes.data, p.ctypes.data, o.ctypes.data, n,
                                               ctypes.byref(got)), "rdf_copy_triples")
         return s[:got.value], p[:got.value], o[:got.value]
+
+    # -- dataset statistics ----------------------------------------------------------------------
+    def copy_histogram(self, n_rows: int | None = None) -> np.ndarray:
+        """The rows of the last histogram call (rdf_copy_histogram), HIST_DTYPE, sorted by (kind, value)."""
+        cap = self.hist_rows if n_rows is None else n_rows
+        out = np.empty(cap, dtype=HIST_DTYPE)
+        got = ctypes.c_uint64()
+        self._check(self.lib.rdf_copy_histogram(self.ptr, out.ctypes.data, cap, ctypes.byref(got)), "rdf_copy_histogram")
+        return out[: got.value]
+
+    def condition_histogram(self) -> np.ndarray:
+        """CountConditions on the resident triples (rdf_condition_histogram): rows (kind, value, times) = ``times``
+        distinct conditions of ``kind`` (1 s, 2 p, 4 o, 3 sp, 5 so, 6 po; 0: all six together) occur in exactly
+        ``value`` triples.  The device time is left in ``self.hist_ms``."""
+        n, ms = ctypes.c_uint64(), ctypes.c_float()
+        self._check(self.lib.rdf_condition_histogram(self.ptr, ctypes.byref(n), ctypes.byref(ms)),
+                    "rdf_condition_histogram")
+        self.hist_rows, self.hist_ms = int(n.value), float(ms.value)
+        return self.copy_histogram()
+
+    def join_histogram(self, projection: str = "spo", use_fis: bool = True) -> np.ndarray:
+        """--create-join-histogram (rdf_join_histogram): rows (0, k, t) = t join lines of exactly k distinct conditions.
+        ``use_fis``: with the frequent conditions of the last :meth:`frequent_conditions` (and the rules of
+        :meth:`association_rules` if it ran); otherwise every value passes (RDF_JH_NO_FIS, resident triples only).
+        The line count is left in ``self.join_lines``, the device time in ``self.hist_ms``."""
+        lines, n, ms = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_float()
+        self._check(self.lib.rdf_join_histogram(self.ptr, projection.encode(), 0 if use_fis else RDF_JH_NO_FIS,
+                                                ctypes.byref(lines), ctypes.byref(n), ctypes.byref(ms)),
+                    "rdf_join_histogram")
+        self.join_lines, self.hist_rows, self.hist_ms = int(lines.value), int(n.value), float(ms.value)
+        return self.copy_histogram()
+
+    def count_literals(self):
+        """CountDistinctValues on the device dictionary of the last parse (rdf_count_literals): (literals, terms);
+        terms - literals are the "URLs"."""
+        lit, terms = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.rdf_count_literals(self.ptr, ctypes.byref(lit), ctypes.byref(terms)), "rdf_count_literals")
+        return int(lit.value), int(terms.value)
 
     def frequent_conditions(self, min_support: int):
         st = FcStats()

@@ -55,6 +55,11 @@ using namespace rdf;
     /* terms' bytes before the re-deduplication, old id -> new id; the new term table and heap, which change places */ \
     /* with nterm_off / nterm_len / ntheap once they are complete (the old ones are then released as scratch) */ \
     B(PARSE, rwkeys) B(PARSE, rwkm) B(PARSE, rwheap) B(PARSE, rwmap) B(PARSE, rwtoff) B(PARSE, rwtlen) B(PARSE, rwnheap) \
+    /* dataset statistics (histo.inl): level-1 keys / join records and level-2 keys with their sort buffers, the sorted */ \
+    /* binary condition keys of a no-FIS join histogram, run-head flags, their scans (hgpos2: the join heads'), run */ \
+    /* starts, the rows before kind 0 is folded in, the rows of the last histogram call, the literal counter */ \
+    B(RUN, hgk) B(RUN, hgk_tmp) B(RUN, hgl) B(RUN, hgl_tmp) B(RUN, hgbin) B(RUN, hgbin_tmp) B(RUN, hgflag) B(RUN, hgpos) \
+    B(RUN, hgpos2) B(RUN, hgstart) B(RUN, hgstage) B(RUN, hgrows) B(RUN, hglit) \
     /* frequent conditions */ \
     B(RUN, frank) B(RUN, fval) B(RUN, fext) \
     B(RUN, cnt) B(SPARE_FC, tkeys) B(RUN, tcnt) B(RUN, bkeys) B(RUN, bkeys_tmp) B(RUN, lkeys) B(RUN, lvals) B(RUN, flags) \
@@ -181,6 +186,8 @@ struct rdf_ctx : CtxBuffers {
     // chunked parse (rdf_parse_begin .. rdf_parse_end): totals so far
     bool parse_open = false;
     u32 rw_form = 0;  // the key lookup of the last rdf_rewrite_terms (RDF_TEST_RW_*; 0: none ran, or it had no keys)
+    bool hist_valid = false;  // hgrows holds the hist_rows rows of the last histogram call (rdf_copy_histogram)
+    u64 hist_rows = 0;
     u32 parse_flags = 0;
     u64 pc_n = 0, pc_V = 0, pc_lines = 0, pc_chunks = 0, pc_heap = 0, pc_slots = 0, pc_growths = 0;
     float pc_ms = 0;
@@ -668,6 +675,7 @@ static void release_run_buffers(rdf_ctx* c, u64 n_next, bool always = false) {
         if (e.cls != BUF_INPUT) b.release();
     });
     c->ws.release();
+    c->hist_valid = false;
     c->dense_on = false;
     c->class_pending = false;
     c->h_runs_valid = false;
@@ -5863,6 +5871,259 @@ rdf_status rdf_copy_binary_keys(rdf_ctx* c, uint64_t* out, uint64_t cap) {
     TRY(load_bkeys(c));
     const u64 m = std::min<u64>(cap, c->h_bkeys.size());
     if (m) memcpy(out, c->h_bkeys.data(), m * 8);
+    return RDF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Dataset statistics (histo.inl): rdf_condition_histogram, rdf_join_histogram, rdf_count_literals.  Buffers of their
+// own (hg*), the workspace and the timing events 6 / 7 only: no pipeline state changes.
+
+// keys <- its m keys sorted on the low `bits` bits (keys / tmp change places when the passes end in tmp)
+static rdf_status h_sort(rdf_ctx* c, DevBuf& keys, DevBuf& tmp, u64 m, int bits) {
+    u64 *k = keys.as<u64>(), *t = tmp.as<u64>();
+    HIP_TRY(c, radix_sort_u64(c->ws, k, t, m, bits, c->stream));
+    if (k != keys.as<u64>()) std::swap(keys, tmp);
+    return RDF_OK;
+}
+
+// runs of equal keys >> shift among the sorted keys[0, m): *R runs, hgstart[r] = first index of run r, hgstart[*R] = m.
+// Leaves the head flags in hgflag and their exclusive scan in `pos` (pos[m] = *R).
+static rdf_status h_run_starts(rdf_ctx* c, const u64* keys, u64 m, int shift, DevBuf& pos, u64* R) {
+    hipStream_t st = c->stream;
+    *R = 0;
+    if (!m) return RDF_OK;
+    TRY(ensure_buf(c, &c->hgflag, m * 4, "allocating hgflag"));
+    TRY(ensure_buf(c, &pos, (m + 1) * 4, "allocating hgpos"));
+    const dim3 g(grid_for(m + 1, RDF_BLOCK, kGrid));
+    hipLaunchKernelGGL(k_histo_heads, g, dim3(RDF_BLOCK), 0, st, keys, m, shift, c->hgflag.as<u32>());
+    HIP_TRY(c, exclusive_scan_u32(c->ws, c->hgflag.as<u32>(), pos.as<u32>(), m, pos.as<u32>() + m, st));
+    u32 runs = 0;
+    TRY(read_u32(c, pos.as<u32>() + m, &runs));
+    ENSURE(c, hgstart, ((u64)runs + 1) * 4);
+    hipLaunchKernelGGL(k_histo_starts, g, dim3(RDF_BLOCK), 0, st, c->hgflag.as<u32>(), pos.as<u32>(), m, c->hgstart.as<u32>());
+    HIP_TRY(c, hipGetLastError());
+    *R = runs;
+    return RDF_OK;
+}
+
+// the m level-2 keys in hgl -> sorted on `bits` bits -> one row per distinct key at out[0, *R) (out: hgstage or hgrows,
+// grown keeping what it holds, from row `at` on)
+static rdf_status h_level2_rows(rdf_ctx* c, u64 m, int bits, DevBuf& out, u64 at, u64* R) {
+    hipStream_t st = c->stream;
+    TRY(h_sort(c, c->hgl, c->hgl_tmp, m, bits));
+    TRY(h_run_starts(c, c->hgl.as<u64>(), m, 0, c->hgpos, R));
+    HIP_TRY(c, out.grow_keep((at + std::max<u64>(*R, 1)) * sizeof(rdf_hist_row), st));
+    if (*R)
+        hipLaunchKernelGGL(k_histo_rows, dim3(grid_for(*R, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->hgl.as<u64>(),
+                           c->hgstart.as<u32>(), *R, out.as<rdf_hist_row>() + at);
+    HIP_TRY(c, hipGetLastError());
+    return RDF_OK;
+}
+
+// one arity of the condition histogram: the 3 n keys in hgk (`bits` bits) -> rows (kind, count, times) at
+// hgstage[at, at + *R)
+static rdf_status h_condition_arity(rdf_ctx* c, bool unary, u64 m, int bits, u32 V, int jb, u64 at, u64* R) {
+    hipStream_t st = c->stream;
+    TRY(h_sort(c, c->hgk, c->hgk_tmp, m, bits));
+    u64 R1 = 0;
+    TRY(h_run_starts(c, c->hgk.as<u64>(), m, 0, c->hgpos, &R1));
+    ENSURE(c, hgl, R1 * 8);
+    ENSURE(c, hgl_tmp, R1 * 8);
+    const dim3 g(grid_for(R1, RDF_BLOCK, kGrid));
+    if (unary)
+        hipLaunchKernelGGL(k_histo_level2<true>, g, dim3(RDF_BLOCK), 0, st, c->hgk.as<u64>(), c->hgstart.as<u32>(), R1, V, jb,
+                           c->hgl.as<u64>());
+    else
+        hipLaunchKernelGGL(k_histo_level2<false>, g, dim3(RDF_BLOCK), 0, st, c->hgk.as<u64>(), c->hgstart.as<u32>(), R1, V, jb,
+                           c->hgl.as<u64>());
+    HIP_TRY(c, hipGetLastError());
+    return h_level2_rows(c, R1, 35, c->hgstage, at, R);
+}
+
+static rdf_status condition_histogram_body(rdf_ctx* c, u64* n_rows) {
+    hipStream_t st = c->stream;
+    const u64 n = c->n, m = 3 * n;
+    const u32 V = c->V ? c->V : 1;
+    const int jb = bits_for(V - 1);
+    *n_rows = 0;
+    if (!n) return RDF_OK;
+    ENSURE(c, hgk, m * 8);
+    ENSURE(c, hgk_tmp, m * 8);
+    const dim3 g(grid_for(n, RDF_BLOCK, kGrid));
+    u64 Ru = 0, Rb = 0;
+    hipLaunchKernelGGL(k_histo_unary_keys, g, dim3(RDF_BLOCK), 0, st, c->s, c->p, c->o, n, V, c->hgk.as<u64>());
+    TRY(h_condition_arity(c, true, m, bits_for(3ull * V - 1), V, jb, 0, &Ru));
+    hipLaunchKernelGGL(k_histo_binary_keys, g, dim3(RDF_BLOCK), 0, st, c->s, c->p, c->o, n, jb, c->hgk.as<u64>());
+    TRY(h_condition_arity(c, false, m, 2 + 2 * jb, V, jb, Ru, &Rb));
+    // kind 0 folded in: every row under its kind and under kind 0, sorted by (kind, count); a kind's distinct counts
+    // number at most sqrt(2 n), so the row index fits its 29 bits
+    const u64 R = Ru + Rb, M = 2 * R;
+    if (R >> HISTO_FOLD_IDX_BITS) return fail(c, RDF_ERR_LIMIT, "condition histogram: too many distinct counts");
+    ENSURE(c, hgl, M * 8);
+    ENSURE(c, hgl_tmp, M * 8);
+    hipLaunchKernelGGL(k_histo_fold_keys, dim3(grid_for(R, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st,
+                       c->hgstage.as<rdf_hist_row>(), R, c->hgl.as<u64>());
+    TRY(h_sort(c, c->hgl, c->hgl_tmp, M, 64));
+    ENSURE(c, hgflag, M * 4);
+    ENSURE(c, hgpos, (M + 1) * 4);
+    const dim3 gm(grid_for(M, RDF_BLOCK, kGrid));
+    hipLaunchKernelGGL(k_histo_fold_flags, gm, dim3(RDF_BLOCK), 0, st, c->hgl.as<u64>(), M, c->hgflag.as<u32>());
+    HIP_TRY(c, exclusive_scan_u32(c->ws, c->hgflag.as<u32>(), c->hgpos.as<u32>(), M, c->hgpos.as<u32>() + M, st));
+    u32 rows = 0;
+    TRY(read_u32(c, c->hgpos.as<u32>() + M, &rows));
+    ENSURE(c, hgrows, std::max<u64>(rows, 1) * sizeof(rdf_hist_row));
+    hipLaunchKernelGGL(k_histo_fold_rows, gm, dim3(RDF_BLOCK), 0, st, c->hgl.as<u64>(), M, c->hgflag.as<u32>(),
+                       c->hgpos.as<u32>(), c->hgstage.as<rdf_hist_row>(), c->hgrows.as<rdf_hist_row>());
+    HIP_TRY(c, hipGetLastError());
+    *n_rows = rows;
+    return RDF_OK;
+}
+
+// the common frame of the two histogram calls: device timing, and the rows become the context's histogram
+static rdf_status histogram_begin(rdf_ctx* c) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->hist_valid = false;
+    HIP_TRY(c, hipEventRecord(c->ev[6], c->stream));
+    return RDF_OK;
+}
+static rdf_status histogram_end(rdf_ctx* c, u64 rows, uint64_t* n_rows, float* ms) {
+    HIP_TRY(c, hipEventRecord(c->ev[7], c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (ms) HIP_TRY(c, hipEventElapsedTime(ms, c->ev[6], c->ev[7]));
+    c->hist_rows = rows;
+    c->hist_valid = true;
+    if (n_rows) *n_rows = rows;
+    return RDF_OK;
+}
+
+rdf_status rdf_condition_histogram(rdf_ctx* c, uint64_t* n_rows, float* ms) {
+    if (!c) return RDF_ERR_ARG;
+    if (c->stage < 1) return fail(c, RDF_ERR_STATE, "rdf_set_triples must be called first");
+    if (3 * c->n >= (1ull << 32)) return fail(c, RDF_ERR_LIMIT, "rdf_condition_histogram: 3 n must be < 2^32 keys");
+    u64 rows = 0;
+    TRY(histogram_begin(c));
+    TRY(condition_histogram_body(c, &rows));
+    return histogram_end(c, rows, n_rows, ms);
+}
+
+static rdf_status join_histogram_body(rdf_ctx* c, int proj, bool fis, u64* n_lines, u64* n_rows) {
+    hipStream_t st = c->stream;
+    const u64 n = c->n;
+    const u32 V = c->V ? c->V : 1;
+    const int jb = bits_for(V - 1);
+    const int nproj = (proj & 1) + ((proj >> 1) & 1) + ((proj >> 2) & 1);
+    *n_lines = *n_rows = 0;
+    if (!n || !nproj) return RDF_OK;
+    const dim3 g(grid_for(n, RDF_BLOCK, kGrid));
+    // binary condition ids: the frequent binary conditions' indices, or (no FIS) first indices in the sorted keys of all
+    // triples' binary conditions
+    u64 nb = c->B;
+    if (!fis) {
+        nb = 3 * n;
+        ENSURE(c, hgbin, nb * 8);
+        ENSURE(c, hgbin_tmp, nb * 8);
+        hipLaunchKernelGGL(k_histo_binary_keys, g, dim3(RDF_BLOCK), 0, st, c->s, c->p, c->o, n, jb, c->hgbin.as<u64>());
+        TRY(h_sort(c, c->hgbin, c->hgbin_tmp, nb, 2 + 2 * jb));
+    }
+    const int cb = std::max(bits_for(6ull * V - 1), bits_for(nb ? nb - 1 : 0));
+    if (jb + cb + 1 > 64) return fail(c, RDF_ERR_LIMIT, "rdf_join_histogram: join + condition bits exceed 64");
+    const u64 cap = 2ull * nproj * n;
+    ENSURE(c, hgflag, n * 4);
+    ENSURE(c, hgpos, (n + 1) * 4);
+    ENSURE(c, hgk, cap * 8);
+    ENSURE(c, hgk_tmp, cap * 8);
+    const u32* frank = fis ? c->frank.as<u32>() : nullptr;
+    const u64* lkeys = fis ? c->lkeys.as<u64>() : nullptr;
+    const u32* lvals = fis ? c->lvals.as<u32>() : nullptr;
+    const u64 lmask = fis ? c->lcap - 1 : 0;
+    const u64* ubin = fis ? nullptr : c->hgbin.as<u64>();
+#define RDF_JH_EMIT(FIS, WRITE)                                                                                             \
+    hipLaunchKernelGGL((k_histo_join_emit<FIS, WRITE>), g, dim3(RDF_BLOCK), 0, st, c->s, c->p, c->o, n, V, frank, lkeys, lvals, \
+                       lmask, ubin, nb, jb, proj, cb, c->hgflag.as<u32>(), c->hgpos.as<u32>(), c->hgk.as<u64>(), cap)
+    if (fis) RDF_JH_EMIT(true, false);
+    else RDF_JH_EMIT(false, false);
+    HIP_TRY(c, exclusive_scan_u32(c->ws, c->hgflag.as<u32>(), c->hgpos.as<u32>(), n, c->hgpos.as<u32>() + n, st));
+    u32 m32 = 0;
+    TRY(read_u32(c, c->hgpos.as<u32>() + n, &m32));
+    const u64 m = m32;
+    if (m > cap) return fail(c, RDF_ERR_HIP, "rdf_join_histogram: more records counted than a triple can emit");
+    if (!m) return RDF_OK;
+    if (fis) RDF_JH_EMIT(true, true);
+    else RDF_JH_EMIT(false, true);
+#undef RDF_JH_EMIT
+    HIP_TRY(c, hipGetLastError());
+    // join-major sort; a line's distinct conditions = the record runs inside its join run
+    TRY(h_sort(c, c->hgk, c->hgk_tmp, m, jb + cb + 1));
+    u64 D = 0, G = 0;
+    TRY(h_run_starts(c, c->hgk.as<u64>(), m, 0, c->hgpos, &D));
+    TRY(h_run_starts(c, c->hgk.as<u64>(), m, cb + 1, c->hgpos2, &G));  // (hgflag: the join heads now)
+    ENSURE(c, hgstart, (G + 1) * 4);
+    hipLaunchKernelGGL(k_histo_join_starts, dim3(grid_for(m + 1, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st,
+                       c->hgflag.as<u32>(), c->hgpos.as<u32>(), c->hgpos2.as<u32>(), m, c->hgstart.as<u32>());
+    ENSURE(c, hgl, G * 8);
+    ENSURE(c, hgl_tmp, G * 8);
+    hipLaunchKernelGGL(k_histo_sizes, dim3(grid_for(G, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->hgstart.as<u32>(), G,
+                       c->hgl.as<u64>());
+    HIP_TRY(c, hipGetLastError());
+    *n_lines = G;
+    return h_level2_rows(c, G, 32, c->hgrows, 0, n_rows);
+}
+
+rdf_status rdf_join_histogram(rdf_ctx* c, const char* projection, uint32_t flags, uint64_t* n_lines, uint64_t* n_rows,
+                              float* ms) {
+    if (!c) return RDF_ERR_ARG;
+    if (flags & ~RDF_JH_NO_FIS) return fail(c, RDF_ERR_ARG, "unknown join histogram flags");
+    const bool fis = !(flags & RDF_JH_NO_FIS);
+    if (c->stage < 1) return fail(c, RDF_ERR_STATE, "rdf_set_triples must be called first");
+    if (fis && c->stage < 2)
+        return fail(c, RDF_ERR_STATE, "rdf_frequent_conditions must be called first (or pass RDF_JH_NO_FIS)");
+    // (a sharded protocol under way, or its finished run: phase 9 stays behind a finished one, nranks until the next
+    // single-GPU group build)
+    if (fis && ((c->sh_phase >= 0 && c->sh_phase != 9) || (c->nranks > 1 && c->stage >= 3)))
+        return fail(c, RDF_ERR_STATE, "rdf_join_histogram reads one GPU's frequent conditions, not a sharded run's");
+    int proj = 7;
+    TRY(parse_projection(c, projection, &proj));
+    if (6 * c->n >= (1ull << 32))
+        return fail(c, RDF_ERR_LIMIT, "rdf_join_histogram: 6 n must be < 2^32 records (join ranges are out of scope)");
+    u64 lines = 0, rows = 0;
+    TRY(histogram_begin(c));
+    TRY(join_histogram_body(c, proj, fis, &lines, &rows));
+    TRY(histogram_end(c, rows, n_rows, ms));
+    if (n_lines) *n_lines = lines;
+    return RDF_OK;
+}
+
+rdf_status rdf_copy_histogram(rdf_ctx* c, rdf_hist_row* out, uint64_t cap, uint64_t* n_copied) {
+    if (!c || (cap && !out)) return RDF_ERR_ARG;
+    if (!c->hist_valid) return fail(c, RDF_ERR_STATE, "no histogram: rdf_condition_histogram or rdf_join_histogram comes first");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const u64 m = std::min<u64>(cap, c->hist_rows);
+    if (m) HIP_TRY(c, ctx_copy(c, out, c->hgrows.p, m * sizeof(rdf_hist_row), hipMemcpyDeviceToHost));
+    if (n_copied) *n_copied = m;
+    return RDF_OK;
+}
+
+rdf_status rdf_count_literals(rdf_ctx* c, uint64_t* n_literals, uint64_t* n_terms) {
+    if (!c) return RDF_ERR_ARG;
+    if (c->parse_open) return fail(c, RDF_ERR_STATE, "a chunked parse is open (rdf_parse_end comes first)");
+    if (c->ingest_sharded) return fail(c, RDF_ERR_STATE, "the dictionary of a sharded ingest is spread over its ranks");
+    if (!c->parsed_dict || c->stage < 1)
+        return fail(c, RDF_ERR_STATE, "the resident dictionary does not come from a device parse");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const u64 V = c->n_terms_parsed;
+    u64 lit = 0;
+    if (V) {
+        ENSURE(c, hglit, 8);
+        HIP_TRY(c, hipMemsetAsync(c->hglit.p, 0, 8, st));
+        hipLaunchKernelGGL(k_histo_literals, dim3(grid_for(V, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st,
+                           (const unsigned char*)(c->dict_in_heap ? c->ntheap.p : c->ntext.p), c->nterm_off.as<u64>(),
+                           c->nterm_len.as<u32>(), V, c->hglit.as<u64>());
+        HIP_TRY(c, hipGetLastError());
+        TRY(read_u64(c, c->hglit.p, &lit));
+    }
+    if (n_literals) *n_literals = lit;
+    if (n_terms) *n_terms = V;
     return RDF_OK;
 }
 

@@ -6,6 +6,8 @@ read + parse N-Triples -> (optional) asciify / shorten URLs -> (optional) distin
 the term rewrite (--asciify-triples, --prefixes: one ``rdf_rewrite_terms`` over the device dictionary) and the three
 middle stages run on the GPU through the C ABI (``include/rdfind_hip.h``); there is no CPU fallback.  With
 ``--host-parser`` the parse and the term rewrite run on the host instead (rdfind_amd/ntriples.py, same results).
+``--create-join-histogram`` (RDFind.scala:449-452) prints the join-line sizes before the traversal
+(``rdf_join_histogram``, on the device); the reference's counting programs are ``python -m rdfind_amd.count``.
 
 Flag names follow ``RDFind.Parameters`` (RDFind.scala:639-721).  Flags that only change how Flink
 executes (and not the result) are accepted and ignored; flags whose semantics are out of scope for
@@ -104,6 +106,9 @@ class RDFind:
             # the rules come out of the frequent-condition plan (FrequentConditionPlanner.scala:102), which only runs
             # with --use-fis (RDFind.scala:290-296); without it their broadcast set is null
             raise ValueError("--use-ars / --ar-output require --use-fis")
+        if self.args.create_join_histogram and self.args.dop > 1:
+            # rdf_join_histogram reads one GPU's triples and frequent conditions; a rank holds a slice of either
+            raise NotImplementedError("--create-join-histogram with -dop > 1")
         self.timings = {}
         self.rewrite_stats = None  # rdf_rewrite_stats of the device term rewrite (--prefixes / --asciify-triples)
 
@@ -122,8 +127,9 @@ class RDFind:
         with open(path, "w", encoding="utf-8") as f:
             f.writelines(ln + "\n" for ln in lines)
 
-    def run(self, out=sys.stdout):
+    def run(self, out=None):
         a = self.args
+        out = sys.stdout if out is None else out  # (the stream of the moment, not the one at import)
         world = int(os.environ.get("WORLD_SIZE", "1"))
         if a.dop > 1 and world == 1:
             return self.launch_ranks(a.dop)
@@ -131,6 +137,8 @@ class RDFind:
         if world > 1:
             if a.find_only_fcs or a.do_only_join:
                 raise NotImplementedError("--find-only-fcs / --do-only-join with -dop > 1")
+            if a.create_join_histogram:
+                raise NotImplementedError("--create-join-histogram with -dop > 1")
             import torch
             import torch.distributed as dist  # the ranks' exchange (rdfind_amd/distributed.py)
             if not dist.is_initialized():  # RDFIND_DIST_BACKEND=gloo: host-staged exchange (rehearsals on one GPU)
@@ -154,18 +162,8 @@ class RDFind:
                 s, p, o, dic = ntriples.read_triples(paths, tabs=a.tabs)
                 n_in = s.shape[0]
                 ctx.set_triples(s, p, o, dic.size)
-            else:  # Parse triples on the device: the host only reads the bytes.  An input of one window goes in one
-                # call (rdf_parse_ntriples), a larger one window by window (rdf_parse_begin / _chunk / _end)
-                windows = ntriples.iter_windows(paths, a.ingest_window)
-                head = list(itertools.islice(windows, 2))
-                if len(head) < 2:
-                    n_in, _, _ = ctx.parse_ntriples(head[0] if head else b"", tabs=a.tabs)
-                else:
-                    def handed_on():  # one by one, so that no window outlives its parse
-                        while head:
-                            yield head.pop(0)
-                        yield from windows
-                    n_in, _, _ = ctx.parse_windows(handed_on(), tabs=a.tabs)
+            else:  # Parse triples on the device: the host only reads the bytes
+                n_in = device_ingest(ctx, paths, a.tabs, a.ingest_window)
                 dic = None  # device dictionary, fetched when needed
             if a.prefixes or a.asciify_triples:  # Asciify triples, Shorten URLs (RDFind.scala:239-267), once per
                 # distinct term: on the device dictionary (rdf_rewrite_terms), or on the host parser's
@@ -219,6 +217,11 @@ class RDFind:
                     self.write_rules(a.ar_output, format_rules(ctx.copy_association_rules(), dic.term))
                 if not a.use_ars:  # rules printed only: frequent conditions again, without the suppression
                     fc = ctx.frequent_conditions(a.support)
+            if a.create_join_histogram:  # RDFind.scala:449-452: after the frequent conditions and the rules, before the
+                # traversal; once, also when the discovery below starts over in pages.  Without --use-fis the
+                # reference's join partners pass every value (CreateJoinPartners.scala:78)
+                for ln in join_histogram_lines(ctx.join_histogram(a.projection, use_fis=a.use_fis)):
+                    print(ln, file=out)
             gs = ctx.build_capture_groups(a.projection)
             if a.do_only_join:
                 return []
@@ -389,6 +392,21 @@ class RDFind:
         return subprocess.run(cmd, env=env).returncode
 
 
+def device_ingest(ctx, paths, tabs, window_bytes):
+    """Parse triples on the device (also rdfind_amd.count's ingest): an input of one window goes in one call
+    (rdf_parse_ntriples), a larger one window by window (rdf_parse_begin / _chunk / _end).  Returns the triples."""
+    windows = ntriples.iter_windows(paths, window_bytes)
+    head = list(itertools.islice(windows, 2))
+    if len(head) < 2:
+        return ctx.parse_ntriples(head[0] if head else b"", tabs=tabs)[0]
+
+    def handed_on():  # one by one, so that no window outlives its parse
+        while head:
+            yield head.pop(0)
+        yield from windows
+    return ctx.parse_windows(handed_on(), tabs=tabs)[0]
+
+
 def _output_path(spec):
     path = spec[5:] if spec.startswith("file:") else spec
     while path.startswith("//"):
@@ -403,6 +421,11 @@ def format_rules(rules, term):
     chars = {1: "s", 2: "p", 4: "o"}
     return sorted(f"[{chars[ta]}={term(va)}] -> [{chars[tc]}={term(vc)}] (support={n},confidence=100.00%)"
                   for ta, tc, va, vc, n in rules.tolist())
+
+
+def join_histogram_lines(rows):
+    """--create-join-histogram's lines (RDFind.scala:451) of rdf_hist_row rows, ascending by join size."""
+    return [f"Join size {k} encountered {t}x" for _, k, t in rows.tolist()]
 
 
 def format_rows(rows, term):
