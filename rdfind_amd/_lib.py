@@ -104,7 +104,13 @@ class PathReport(ctypes.Structure):
     _fields_ = [("k1_form", ctypes.c_uint32), ("k2_form", ctypes.c_uint32), ("k3_form", ctypes.c_uint32),
                 ("dense_on", ctypes.c_uint32), ("light_stage", ctypes.c_uint32), ("light_hiocc", ctypes.c_uint32),
                 ("n_dense", ctypes.c_uint64), ("n_dense_eligible", ctypes.c_uint64),
-                ("n_dedup_members", ctypes.c_uint64)]
+                ("n_dedup_members", ctypes.c_uint64),
+                ("n_light_items", ctypes.c_uint64), ("n_packed_octets", ctypes.c_uint64),
+                ("n_mseg_chunks", ctypes.c_uint64), ("n_multi_items", ctypes.c_uint64),
+                ("n_light_survivors", ctypes.c_uint64),
+                ("light_npx", ctypes.c_uint32), ("packed_npx", ctypes.c_uint32), ("light_ordered", ctypes.c_uint32),
+                ("light_side", ctypes.c_uint32), ("light_two_pass", ctypes.c_uint32), ("sig_on", ctypes.c_uint32),
+                ("piv2_on", ctypes.c_uint32)]
 
 
 class ResultLayout(ctypes.Structure):
@@ -633,12 +639,17 @@ class Context:
 
     def test_paths(self) -> dict:
         """Which alternative paths the last completed run took (rdf_test_paths): the K1 / K2 / K3 forms by name,
-        dense_on, light_stage, light_hiocc, n_dense, n_dense_eligible, n_dedup_members."""
+        dense_on, light_stage, light_hiocc, n_dense, n_dense_eligible, n_dedup_members, and what the light launches
+        were given, summed over the run's pages, ranges and light passes: n_light_items (k_light work items),
+        n_packed_octets (k_light_packed), n_mseg_chunks (k_light_mseg_emit), n_multi_items (items of dependents with
+        several chunks), n_light_survivors (pass B's input), light_npx / packed_npx (extra pivots checked), and the
+        flags light_ordered, light_side, light_two_pass, sig_on, piv2_on."""
         r = PathReport()
         self._check(self._test_fn("rdf_test_paths")(self.ptr, ctypes.byref(r)), "rdf_test_paths")
         d = _struct_dict(r)
         d["k1_form"], d["k2_form"], d["k3_form"] = K1_FORMS[r.k1_form], K2_FORMS[r.k2_form], K3_FORMS[r.k3_form]
-        for name in ("dense_on", "light_stage", "light_hiocc"):
+        for name in ("dense_on", "light_stage", "light_hiocc", "light_ordered", "light_side", "light_two_pass", "sig_on",
+                     "piv2_on"):
             d[name] = bool(d[name])
         return d
 

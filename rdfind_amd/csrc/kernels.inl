@@ -2087,12 +2087,15 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_light_packed(u64 nvblk, CindView 
 
 
 #ifdef RDF_LIGHT_STATS
-// dev instrumentation (make stats): one 16 x u32 record per k_light work item, written by lane 0 without atomics:
+// instrumented variant (librdfind_hip_stats.so): one 24 x u32 record per k_light work item, written by lane 0 without
+// atomics:
 // [0] dep [1] groups of the dependent [2] groups of this segment [3] nseg [4] pivot size [5] alive0 [6] alive at exit
-// [7] 64-group windows visited [8] groups taken by the serial path [9] batch rounds [10] sum of batch search depths
-// [11] light groups in visited windows [12..13] clock64 cycles [14] sum of visited light group sizes [15] largest
+// [7] 64-group windows visited [8] groups taken by the serial path | swept windows << 16 [9] batch rounds
+// [10] sum of batch search depths [11] light groups in visited windows [12..13] clock64 cycles
+// [14] sum of visited light group sizes [15] largest [16..21] phase cycles / 256 (below)
+// [22] rounds of the dense-serial loop (LIGHT_DENSE_BATCH bitmap rows each) [23] windows taken by the staged-row path
 __device__ u32* g_item_rec;
-#define LSTAT_T0 const unsigned long long lstat_t0 = clock64(); u32 ls_win = 0, ls_ser = 0, ls_bat = 0, ls_dep = 0, ls_lg = 0, ls_gs = 0, ls_gmax = 0; \
+#define LSTAT_T0 const unsigned long long lstat_t0 = clock64(); u32 ls_win = 0, ls_ser = 0, ls_bat = 0, ls_dep = 0, ls_lg = 0, ls_gs = 0, ls_gmax = 0, ls_dser = 0, ls_row = 0; \
     unsigned long long ls_ph[6] = {0, 0, 0, 0, 0, 0}, ls_tic = 0
 // phase timers (cycles): [0] second pivot, [1] window metadata loads, [2] dense groups, [3] serial groups, [4] sweeps,
 // [5] batches
@@ -2103,6 +2106,8 @@ __device__ u32* g_item_rec;
     ls_gmax = m_ > ls_gmax ? m_ : ls_gmax; } while (0)
 #define LSTAT_SER(k) (ls_ser += (k))
 #define LSTAT_BAT(depth) do { ++ls_bat; ls_dep += (depth); } while (0)
+#define LSTAT_DSER() (++ls_dser)
+#define LSTAT_ROW() (++ls_row)
 #else
 #define LSTAT_T0 do { } while (0)
 #define LSTAT_TIC() do { } while (0)
@@ -2110,6 +2115,8 @@ __device__ u32* g_item_rec;
 #define LSTAT_WIN(lmask, gsz) do { } while (0)
 #define LSTAT_SER(k) do { } while (0)
 #define LSTAT_BAT(depth) do { } while (0)
+#define LSTAT_DSER() do { } while (0)
+#define LSTAT_ROW() do { } while (0)
 #endif
 
 // one batch of the group-parallel window: the next K alive candidates (taken from todo) searched in every lane's
@@ -2370,6 +2377,7 @@ __device__ inline void k_light_body(u64 vblk, CindView v, const u32* __restrict_
                 // per group would make each load wait for the previous one's result)
                 u64 t = dm;
                 while (t && alive) {
+                    LSTAT_DSER();
                     const bool mine = (alive >> lane) & 1ull;
                     u32 wv[LIGHT_DENSE_BATCH];
 #pragma unroll
@@ -2424,6 +2432,7 @@ __device__ inline void k_light_body(u64 vblk, CindView v, const u32* __restrict_
                 // every light group of the window is small: each lane copies its group into its own LDS row with
                 // <= 9 aligned 16-B loads, then the alive candidates are searched in LDS (instead of A x log2 n
                 // divergent global loads)
+                LSTAT_ROW();
                 u32* row = s_light[threadIdx.x / RDF_WAVE] + lane * LIGHT_SMALL;  // odd stride: rows spread over banks
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // earlier reads of the rows precede the refill
                 __builtin_amdgcn_wave_barrier();
@@ -2488,7 +2497,8 @@ __device__ inline void k_light_body(u64 vblk, CindView v, const u32* __restrict_
                              (u32)dt, (u32)(dt >> 32), ls_gs, ls_gmax};
         for (int k = 0; k < 16; ++k) r[k] = rec[k];
         for (int k = 0; k < 6; ++k) r[16 + k] = (u32)(ls_ph[k] >> 8);  // phase cycles / 256
-        r[22] = r[23] = 0;
+        r[22] = ls_dser;
+        r[23] = ls_row;
     }
 #endif
     const u64 oct0 = choff[d] + chunk * 8 - ob;  // first octet slot of this chunk

@@ -259,6 +259,13 @@ struct rdf_ctx : CtxBuffers {
     u64 n_dense_eligible = 0;             // groups d_dense_flags numbered (n_dense: the rows d_dense_build gave a bitmap)
     // which alternative ran at the run's decision points (RDF_TEST_K1_* / K2_* / K3_*, test_abi.h; 0: none yet)
     u32 path_k1 = 0, path_k2 = 0, path_k3 = 0;
+    // what the light launches of the last discovery were given (d_light_kernels; sums over its pages, ranges and
+    // passes), for rdf_test_paths
+    struct LightPaths {
+        u64 items = 0, packed_octets = 0, mseg_chunks = 0;  // WI, WP, WM
+        int light_npx = 0, packed_npx = 0;                  // extra pivots of the last k_light / k_light_packed launch
+        bool ordered = false, side = false, two_pass = false;
+    } lpaths;
     bool sig_on = false;  // lsig holds this run's signatures (RDFIND_SIG=0 turns the filter off)
     bool sig_packed = false;  // the packed light path tests them too (RDFIND_SIG=1; default 2: k_light only)
     bool piv2_on = false;     // piv2 holds this run's second pivots
@@ -2965,6 +2972,8 @@ static rdf_status d_pivot_local(rdf_ctx* c, CindView& v) {
     const u32 C = c->C;
     HIP_TRY(c, hipEventRecord(c->ev[4], st));
     HIP_TRY(c, hipMemsetAsync(c->scal.p, 0, 16 * sizeof(u64), st));
+    c->lpaths = {};  // a discovery starts
+    c->n_light_survivors = c->n_multi_items = 0;
     ENSURE(c, pivot, std::max<u64>(C, 1) * 4);
     ENSURE(c, nchl, std::max<u64>(C, 1) * 4);
     ENSURE(c, nchh, std::max<u64>(C, 1) * 4);
@@ -3190,6 +3199,11 @@ static rdf_status d_light_kernels(rdf_ctx* c, const CindView& v, const u32* pivo
     // the packed dependents on the side stream, beside k_light (disjoint output octets): their blocks fill the SIMDs
     // k_light's long items leave idle (RDFIND_LIGHT_SIDE=0: one stream)
     const bool side = c->sw.light_side && WP && WI;
+    c->lpaths.items += WI;
+    c->lpaths.packed_octets += WP;
+    c->lpaths.mseg_chunks += WM;
+    c->lpaths.side |= side;
+    if (WP) c->lpaths.packed_npx = vp.npx;
     if (side) {
         HIP_TRY(c, hipEventRecord(c->ev_fork, st));
         HIP_TRY(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
@@ -3221,6 +3235,8 @@ static rdf_status d_light_kernels(rdf_ctx* c, const CindView& v, const u32* pivo
                                c->iexcl.as<u32>(), WI, c->iorder.as<u32>());
             order = c->iorder.as<u32>();
         }
+        c->lpaths.light_npx = vl.npx;
+        c->lpaths.ordered |= order != nullptr;
         hipLaunchKernelGGL(kl, dim3(vgrid(wave_blocks(WI))), dim3(RDF_BLOCK),
                            0, st, (u64)wave_blocks(WI), vl, pivot, c->itoffl.as<u64>(), c->item_dep.as<u32>(), c->choffl.as<u64>(),
                            r.i0, WI, ob, c->dead.as<u64>(), slots.as<u64>(), counts.as<u32>(), order);
@@ -3831,6 +3847,7 @@ rdf_status rdf_discover_cinds(rdf_ctx* c, uint32_t flags, rdf_cind_stats* stats)
     TRY(d_chunks(c, &WL, &WH, &WI, &WP));
     c->n_light_survivors = 0;
     const bool two = use_two_pass(c, WI);
+    c->lpaths.two_pass = two;
     if (two) TRY(d_light_two_pass(c, v, WI, WL, WP, &E, c->pivot.as<u32>()));
     else TRY(d_light(c, v, WI, WL, WP, &E, c->pivot.as<u32>()));
     bool indexed = false;

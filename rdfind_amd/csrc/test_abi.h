@@ -70,6 +70,20 @@ typedef struct rdf_test_path_report {
     uint64_t n_dense;              /* light groups with a bitmap row */
     uint64_t n_dense_eligible;     /* ... of those large enough for one (the byte budget may hold fewer) */
     uint64_t n_dedup_members;      /* light dependents that took their class representative's refs */
+    /* The light launches of the last discovery: sums over its pages, dependent ranges and (two light passes) both
+     * passes; the npx fields are those of the last launch of that kernel. */
+    uint64_t n_light_items;        /* k_light work items (dependent x chunk of 64 candidates x segment of groups) */
+    uint64_t n_packed_octets;      /* k_light_packed output octets */
+    uint64_t n_mseg_chunks;        /* chunks of multi-segment dependents (k_light_mseg_emit) */
+    uint64_t n_multi_items;        /* k_light items of dependents with several chunks (unpaged single-GPU runs; else 0) */
+    uint64_t n_light_survivors;    /* two light passes: pass A's tagged survivors, the input of pass B */
+    uint32_t light_npx;            /* extra pivots k_light checked */
+    uint32_t packed_npx;           /* ... and k_light_packed */
+    uint32_t light_ordered;        /* k_light got an issue order (k_light_order) */
+    uint32_t light_side;           /* k_light_packed ran on the side stream beside k_light */
+    uint32_t light_two_pass;       /* the two light passes */
+    uint32_t sig_on;               /* the run computed light-group signatures */
+    uint32_t piv2_on;              /* ... and second pivots */
 } rdf_test_path_report;
 
 rdf_status rdf_test_paths(rdf_ctx* ctx, rdf_test_path_report* out);

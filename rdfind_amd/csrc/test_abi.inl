@@ -191,6 +191,18 @@ rdf_status rdf_test_paths(rdf_ctx* c, rdf_test_path_report* out) {
     r.n_dense = c->n_dense;
     r.n_dense_eligible = c->n_dense_eligible;
     r.n_dedup_members = c->n_dedup_members;
+    r.n_light_items = c->lpaths.items;
+    r.n_packed_octets = c->lpaths.packed_octets;
+    r.n_mseg_chunks = c->lpaths.mseg_chunks;
+    r.n_multi_items = c->n_multi_items;
+    r.n_light_survivors = c->n_light_survivors;
+    r.light_npx = (uint32_t)c->lpaths.light_npx;
+    r.packed_npx = (uint32_t)c->lpaths.packed_npx;
+    r.light_ordered = c->lpaths.ordered ? 1 : 0;
+    r.light_side = c->lpaths.side ? 1 : 0;
+    r.light_two_pass = c->lpaths.two_pass ? 1 : 0;
+    r.sig_on = c->sig_on ? 1 : 0;
+    r.piv2_on = c->piv2_on ? 1 : 0;
     *out = r;
     return RDF_OK;
 }

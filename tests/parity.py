@@ -8,7 +8,9 @@
 * ``assert_rows_equal(ctx, d, ...)``: exact row-by-row parity of the current result with the materializing oracle, as
   sorted packed (dep, ref) keys + supports (vectorized; a Python set of 10^7 tuples took ~40 s per check);
 * ``dataset_npz(cfg, scale)``: the same input saved once as .npy files, for child processes that must start fresh
-  (switches read when the context is created) without regenerating it.
+  (switches read when the context is created) without regenerating it;
+* ``shape_rows(sh, ...)`` / ``assert_shape_rows(ctx, sh, ...)``: the oracle's sorted packed rows of a near-miss shape
+  (tests/light_shapes.py) per (shape, mode, projection), cached for the session, and the row-exact comparison with them.
 """
 from __future__ import annotations
 
@@ -109,3 +111,59 @@ def load_npz(path: str):
     s, p, o = (np.load(os.path.join(path, n + ".npy"), mmap_mode="r") for n in ("s", "p", "o"))
     nv, ms = (int(x) for x in np.load(os.path.join(path, "meta.npy")))
     return s, p, o, nv, ms
+
+
+_SHAPE_ROWS: dict = {}
+
+
+def shape_rows(sh, strategy: int = 1, clean: bool = True, projection: str = "s"):
+    """(sorted dep << 32 | ref keys, supports in that order) of the oracle on a light_shapes.Shape; cached per session.
+    Mode (1, False), the exact-candidate S2L raw output, has only the Python restatement as its oracle (as in
+    tests/test_gpu.py expected_set); its rows are turned into capture ids with the C oracle's binary-key table (both
+    index the sorted frequent binary keys)."""
+    key = (sh.name, strategy, bool(clean), projection)
+    if key in _SHAPE_ROWS:
+        return _SHAPE_ROWS[key]
+    if strategy == 1 and not clean:
+        from oracle import rdfind_oracle as R
+        from rdfind_amd import codes
+        tr = list(zip(sh.s.tolist(), sh.p.tolist(), sh.o.tolist()))
+        uf = R.frequent_unary_conditions(tr, sh.min_support)
+        v = R.all_at_once(R.join_lines(tr, uf, R.frequent_binary_conditions(tr, uf, sh.min_support), projection),
+                          sh.min_support, False, literal_implies=False)
+        cinds = R.cind_set(R.s2l_exact_raw(v))
+        _, bkeys, _ = C.run(sh.s, sh.p, sh.o, sh.num_terms, sh.min_support, 0, False, projection)
+        V = sh.num_terms
+
+        def cap(code, v1, v2):
+            if v2 is None:
+                return codes.UNARY_TYPE_INDEX[code] * V + v1
+            k = (codes.BINARY_TYPE_INDEX[code] << 62) | (v1 << 31) | v2
+            j = int(np.searchsorted(bkeys, np.uint64(k)))
+            assert j < len(bkeys) and int(bkeys[j]) == k
+            return 6 * V + j
+
+        rows = np.zeros(len(cinds), dtype=[("dep", "<u4"), ("ref", "<u4"), ("support", "<u4")])
+        for i, (dt, d1, d2, rt, r1, r2, sup) in enumerate(cinds):
+            rows[i] = (cap(dt, d1, d2), cap(rt, r1, r2), sup)
+    else:
+        rows, _, _ = C.run(sh.s, sh.p, sh.o, sh.num_terms, sh.min_support, strategy, clean, projection)
+    _SHAPE_ROWS[key] = packed(rows)
+    return _SHAPE_ROWS[key]
+
+
+def assert_shape_rows(ctx, sh, strategy: int = 1, clean: bool = True, projection: str = "s", what=None):
+    """Every row of the context's current result equals the oracle's rows of the shape."""
+    ek, es = shape_rows(sh, strategy, clean, projection)
+    gk, gs = packed(ctx.copy_cinds())
+    assert gk.shape[0] == ek.shape[0], (sh.name, strategy, clean, projection, what, gk.shape[0], ek.shape[0],
+                                        _first_diff(gk, ek))
+    bad = np.nonzero(gk != ek)[0]
+    assert bad.size == 0, (sh.name, strategy, clean, projection, what, _first_diff(gk, ek))
+    np.testing.assert_array_equal(gs, es)
+
+
+def _first_diff(gk, ek):
+    """A few (dep, ref) pairs only the device has, and a few only the oracle has."""
+    pair = lambda k: [(int(x) >> 32, int(x) & 0xFFFFFFFF) for x in k[:4]]
+    return {"device_only": pair(np.setdiff1d(gk, ek)), "oracle_only": pair(np.setdiff1d(ek, gk))}
