@@ -499,6 +499,52 @@ rdf_status rdf_join_histogram(rdf_ctx* ctx, const char* projection, uint32_t fla
  * distributed one of a sharded ingest). */
 rdf_status rdf_count_literals(rdf_ctx* ctx, uint64_t* n_literals, uint64_t* n_terms);
 
+/*
+ * Result statistics on the device: what a CIND result contains, without expanding it.  Integer reductions over the
+ * result as it lies in HBM; the class part (members x shared lists) is counted in O(members + list refs) per class and
+ * stays pending.  Rows are rdf_hist_row, ascending by (kind, value), read with rdf_copy_histogram: they share the
+ * dataset statistics' row buffer and lifetime.
+ *   RDF_CS_SHAPE     value = dep_code << 8 | ref_code (capture codes 10, 12, 17, 20, 33, 34, 14, 21, 35); times = CINDs
+ *   RDF_CS_SUPPORT   value = support;  times = CINDs whose dependent has that support
+ *   RDF_CS_REFS      value = r >= 1;   times = dependents with exactly r referenced captures
+ *   RDF_CS_INDEGREE  value = d >= 1;   times = captures referenced by exactly d CINDs
+ * The sums agree: sum times(kind 1) = sum times(kind 2) = sum value * times(kind 3) = sum value * times(kind 4) = CINDs.
+ *
+ *   rdf_cind_stats_begin  zeroes the accumulators (per compact capture id: its refs as a dependent, the CINDs that
+ *                         reference it; 81 shape cells).  Needs the capture table of a completed rdf_discover_cinds /
+ *                         rdf_run, or of a prepared rdf_discover_cinds_paged (RDF_ERR_STATE otherwise).
+ *   rdf_cind_stats_add    adds the current result: the whole result, or the current page of a paged run (the pages
+ *                         partition the dependents and keep the compact ids, so the accumulators add up over them).
+ *                         Adding the same result or page twice counts it twice.
+ *   rdf_cind_stats_end    turns the accumulators into rows and the top list and closes the accumulation; *n_rows
+ *                         receives the row count, *ms (optional) the summed device time of the add calls and this one.
+ *   rdf_cind_histogram    begin + add + end on the current result.
+ *   rdf_copy_top_refs     after _end: the captures with in-degree > 0, descending by in-degree, ties by ascending
+ *                         capture id (external ids, rdf_decode_capture); copies the first min(cap, count) of them.
+ *                         RDF_ERR_STATE without a completed _end, or once the capture table it names is gone.
+ * add / end without an open begin: RDF_ERR_STATE.  Whatever rebuilds the capture table abandons an open accumulation:
+ * new triples, rdf_frequent_conditions, rdf_build_capture_groups, a new discovery (paged or not), rdf_shard_begin,
+ * rdf_release_scratch.  rdf_next_page does not.  Single GPU: after a sharded run every one of these calls returns
+ * RDF_ERR_STATE (a rank holds its own dependents only, and the in-degree of a capture would need a collective over
+ * capture ids).
+ * Each call leaves the stage and the result as they were, except that add writes the heavy-bits form's deferred refs
+ * into the result buffer as rdf_cind_checksum does; a pending class part stays pending.
+ */
+#define RDF_CS_SHAPE 1u
+#define RDF_CS_SUPPORT 2u
+#define RDF_CS_REFS 3u
+#define RDF_CS_INDEGREE 4u
+rdf_status rdf_cind_stats_begin(rdf_ctx* ctx);
+rdf_status rdf_cind_stats_add(rdf_ctx* ctx);
+rdf_status rdf_cind_stats_end(rdf_ctx* ctx, uint64_t* n_rows, float* ms);
+rdf_status rdf_cind_histogram(rdf_ctx* ctx, uint64_t* n_rows, float* ms);
+typedef struct {
+    uint32_t capture;   /* external capture id (rdf_decode_capture) */
+    uint32_t pad;
+    uint64_t cinds;     /* CINDs that reference it */
+} rdf_top_ref;
+rdf_status rdf_copy_top_refs(rdf_ctx* ctx, rdf_top_ref* out, uint64_t cap, uint64_t* n_copied);
+
 /* Device time (ms) of the last call of each stage: [0] fc, [1] groups, [2] cinds. */
 rdf_status rdf_stage_times(rdf_ctx* ctx, float* ms3);
 /* Device time (ms) of each kernel family (RDF_T_*) in the last calls; count <= RDF_NUM_TIMERS. */

@@ -37,14 +37,17 @@ EXPORTED_SYMBOLS = (
     "rdf_copy_result_refs_async", "rdf_handover_wait", "rdf_set_result_form", "rdf_heavy_chunk_count",
     "rdf_copy_result_heavy", "rdf_parse_begin", "rdf_parse_chunk", "rdf_parse_end", "rdf_copy_term_heap",
     "rdf_rewrite_terms", "rdf_condition_histogram", "rdf_join_histogram", "rdf_copy_histogram", "rdf_count_literals",
+    "rdf_cind_stats_begin", "rdf_cind_stats_add", "rdf_cind_stats_end", "rdf_cind_histogram", "rdf_copy_top_refs",
 )
+# rdf_hist_row kinds of the result statistics (rdf_cind_histogram)
+RDF_CS_SHAPE, RDF_CS_SUPPORT, RDF_CS_REFS, RDF_CS_INDEGREE = 1, 2, 3, 4
 RDF_JH_NO_FIS = 1
 RDF_RW_ASCIIFY = 1
 RDF_NT_TABS = 1
 
 # the test-only entry points of rdfind_amd/csrc/test_abi.h (not part of the product ABI)
 TEST_SYMBOLS = ("rdf_test_scan", "rdf_test_scan_batch", "rdf_test_radix", "rdf_test_radix_passes", "rdf_test_paths",
-                "rdf_test_rewrite_form")
+                "rdf_test_rewrite_form", "rdf_test_cind_stats_times")
 REWRITE_FORMS = {0: None, 1: "lds", 2: "global"}
 SCAN_U32_U32, SCAN_U32_U64, SCAN_U64_U64 = range(3)
 SCAN_DTYPES = {SCAN_U32_U32: (np.uint32, np.uint32), SCAN_U32_U64: (np.uint32, np.uint64),
@@ -147,6 +150,8 @@ RULE_DTYPE = np.dtype([("antecedent_type", "<u4"), ("consequent_type", "<u4"), (
 CIND_DTYPE = np.dtype([("dep", "<u4"), ("ref", "<u4"), ("support", "<u4")])
 # rdf_hist_row (include/rdfind_hip.h): one histogram row, sorted by (kind, value)
 HIST_DTYPE = np.dtype([("kind", "<u4"), ("value", "<u4"), ("times", "<u8")])
+# rdf_top_ref (include/rdfind_hip.h): a referenced capture (external id) and the CINDs that reference it
+TOP_DTYPE = np.dtype([("capture", "<u4"), ("pad", "<u4"), ("cinds", "<u8")])
 # rdf_cind_row (include/rdfind_hip.h): the reference's Cind shape with term ids
 ROW_DTYPE = np.dtype([("dep_capture_type", "<u4"), ("dep_value1", "<u4"), ("dep_value2", "<u4"),
                       ("ref_capture_type", "<u4"), ("ref_value1", "<u4"), ("ref_value2", "<u4"), ("support", "<u4")])
@@ -197,6 +202,11 @@ def load():
                                      ctypes.POINTER(ctypes.c_float)]),
         "rdf_copy_histogram": (i32, [P, P, u64, ctypes.POINTER(u64)]),
         "rdf_count_literals": (i32, [P, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "rdf_cind_stats_begin": (i32, [P]),
+        "rdf_cind_stats_add": (i32, [P]),
+        "rdf_cind_stats_end": (i32, [P, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_float)]),
+        "rdf_cind_histogram": (i32, [P, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_float)]),
+        "rdf_copy_top_refs": (i32, [P, P, u64, ctypes.POINTER(u64)]),
         "rdf_frequent_conditions": (i32, [P, u32, ctypes.POINTER(FcStats)]),
         "rdf_build_capture_groups": (i32, [P, ctypes.c_char_p, ctypes.POINTER(GroupStats)]),
         "rdf_discover_cinds": (i32, [P, u32, ctypes.POINTER(CindStats)]),
@@ -254,6 +264,7 @@ def load():
         "rdf_test_radix_passes": (ctypes.c_int, [ctypes.c_int]),
         "rdf_test_paths": (i32, [P, ctypes.POINTER(PathReport)]),
         "rdf_test_rewrite_form": (i32, [P, ctypes.POINTER(u32)]),
+        "rdf_test_cind_stats_times": (i32, [P, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None) if name in TEST_SYMBOLS else getattr(lib, name)
@@ -502,6 +513,49 @@ class Context:
         lit, terms = ctypes.c_uint64(), ctypes.c_uint64()
         self._check(self.lib.rdf_count_literals(self.ptr, ctypes.byref(lit), ctypes.byref(terms)), "rdf_count_literals")
         return int(lit.value), int(terms.value)
+
+    # -- result statistics -----------------------------------------------------------------------
+    def cind_stats_begin(self):
+        """rdf_cind_stats_begin: zeroes the accumulators of the result statistics (after a discovery, or a prepared
+        paged one)."""
+        self._check(self.lib.rdf_cind_stats_begin(self.ptr), "rdf_cind_stats_begin")
+
+    def cind_stats_add(self):
+        """rdf_cind_stats_add: adds the current result (the whole result, or the current page) to the statistics."""
+        self._check(self.lib.rdf_cind_stats_add(self.ptr), "rdf_cind_stats_add")
+
+    def cind_stats_end(self) -> np.ndarray:
+        """rdf_cind_stats_end: the rows (kind, value, times) of the accumulated statistics, HIST_DTYPE sorted by
+        (kind, value): kind 1 value = dep_code << 8 | ref_code, times = CINDs; 2 value = support, times = CINDs of
+        dependents with it; 3 value = r, times = dependents with r refs; 4 value = d, times = captures referenced by d
+        CINDs.  The summed device time of the add calls and this one is left in ``self.hist_ms``."""
+        n, ms = ctypes.c_uint64(), ctypes.c_float()
+        self._check(self.lib.rdf_cind_stats_end(self.ptr, ctypes.byref(n), ctypes.byref(ms)), "rdf_cind_stats_end")
+        self.hist_rows, self.hist_ms = int(n.value), float(ms.value)
+        return self.copy_histogram()
+
+    def cind_histogram(self) -> np.ndarray:
+        """rdf_cind_histogram: begin + add + end on the current result; rows as :meth:`cind_stats_end`, the device time
+        in ``self.hist_ms``.  A pending class part is counted unexpanded and stays pending."""
+        n, ms = ctypes.c_uint64(), ctypes.c_float()
+        self._check(self.lib.rdf_cind_histogram(self.ptr, ctypes.byref(n), ctypes.byref(ms)), "rdf_cind_histogram")
+        self.hist_rows, self.hist_ms = int(n.value), float(ms.value)
+        return self.copy_histogram()
+
+    def top_refs(self, k: int) -> np.ndarray:
+        """rdf_copy_top_refs: the k most referenced captures of the last statistics as (capture, cinds) rows
+        (TOP_DTYPE; external capture ids), descending by cinds, ties by ascending capture id."""
+        out = np.zeros(max(int(k), 0), dtype=TOP_DTYPE)
+        got = ctypes.c_uint64()
+        self._check(self.lib.rdf_copy_top_refs(self.ptr, out.ctypes.data, out.shape[0], ctypes.byref(got)),
+                    "rdf_copy_top_refs")
+        return out[: got.value][["capture", "cinds"]]
+
+    def cind_stats_times(self):
+        """(explicit, class, end) device ms of the last result statistics (rdf_test_cind_stats_times)."""
+        arr = (ctypes.c_float * 3)()
+        self._check(self._test_fn("rdf_test_cind_stats_times")(self.ptr, arr), "rdf_test_cind_stats_times")
+        return list(arr)
 
     def frequent_conditions(self, min_support: int):
         st = FcStats()

@@ -60,6 +60,10 @@ using namespace rdf;
     /* starts, the rows before kind 0 is folded in, the rows of the last histogram call, the literal counter */ \
     B(RUN, hgk) B(RUN, hgk_tmp) B(RUN, hgl) B(RUN, hgl_tmp) B(RUN, hgbin) B(RUN, hgbin_tmp) B(RUN, hgflag) B(RUN, hgpos) \
     B(RUN, hgpos2) B(RUN, hgstart) B(RUN, hgstage) B(RUN, hgrows) B(RUN, hglit) \
+    /* result statistics (cindstats.inl): per compact capture its refs as a dependent, the CINDs referencing it and */ \
+    /* its code index; the 81 shape cells + 2 counters; the sorted top-list keys; the support runs' scanned weights */ \
+    /* (rows and sort scratch: the hg* buffers above) */ \
+    B(RUN, csnref) B(RUN, csindeg) B(RUN, cscode) B(RUN, cscell) B(RUN, cstop) B(RUN, cstop_tmp) B(RUN, cswsum) \
     /* frequent conditions */ \
     B(RUN, frank) B(RUN, fval) B(RUN, fext) \
     B(RUN, cnt) B(SPARE_FC, tkeys) B(RUN, tcnt) B(RUN, bkeys) B(RUN, bkeys_tmp) B(RUN, lkeys) B(RUN, lvals) B(RUN, flags) \
@@ -188,6 +192,12 @@ struct rdf_ctx : CtxBuffers {
     u32 rw_form = 0;  // the key lookup of the last rdf_rewrite_terms (RDF_TEST_RW_*; 0: none ran, or it had no keys)
     bool hist_valid = false;  // hgrows holds the hist_rows rows of the last histogram call (rdf_copy_histogram)
     u64 hist_rows = 0;
+    // result statistics (cindstats.inl): an accumulation is open between rdf_cind_stats_begin and _end and is abandoned
+    // wherever `paged` is reset, the places that rebuild the capture table; cstop holds the top list of the last _end
+    bool cs_open = false, cs_top_valid = false;
+    u64 cs_top_n = 0;
+    float cs_ms[3] = {0, 0, 0};  // device time of the open accumulation: explicit passes, class passes, end
+    hipEvent_t cs_ev[3] = {};
     u32 parse_flags = 0;
     u64 pc_n = 0, pc_V = 0, pc_lines = 0, pc_chunks = 0, pc_heap = 0, pc_slots = 0, pc_growths = 0;
     float pc_ms = 0;
@@ -616,6 +626,7 @@ rdf_status rdf_ctx_create(int device, rdf_ctx** out) {
     if (e == hipSuccess) e = hipHostMalloc((void**)&c->hread, 16 * sizeof(u64), hipHostMallocMapped | hipHostMallocCoherent);
     if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&c->hread_d, c->hread, 0);
     for (int i = 0; i < 8 && e == hipSuccess; ++i) e = hipEventCreate(&c->ev[i]);
+    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&c->cs_ev[i]);
     for (int i = 0; i < 2 * RDF_NUM_TIMERS * rdf_ctx::kTSeg && e == hipSuccess; ++i) e = hipEventCreate(&c->tev[i]);
     if (e != hipSuccess) {
         rdf_ctx_destroy(c);
@@ -636,6 +647,8 @@ void rdf_ctx_destroy(rdf_ctx* c) {
     if (c->hscal) (void)hipHostFree(c->hscal);
     if (c->hread) (void)hipHostFree(c->hread);
     for (auto& e : c->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : c->cs_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : c->tev)
         if (e) (void)hipEventDestroy(e);
@@ -677,7 +690,7 @@ static void release_run_buffers(rdf_ctx* c, u64 n_next, bool always = false) {
     const u64 held = held_bytes(c) - class_bytes(c, BUF_INPUT);
     if (!always && held <= std::max<u64>(4ull << 30, n_next << 10)) return;
     (void)hipStreamSynchronize(c->stream);
-    c->paged = false;
+    c->paged = c->cs_open = c->cs_top_valid = false;
     for_each_buf(c, [](DevBuf& b, const BufEntry& e) {
         if (e.cls != BUF_INPUT) b.release();
     });
@@ -696,7 +709,7 @@ rdf_status rdf_release_scratch(rdf_ctx* c) {
     TRY(hv_wait(c, true));
     release_run_buffers(c, 0, true);
     (void)hipGetLastError();  // an out-of-memory failure before this call is not the next call's error
-    c->paged = false;
+    c->paged = c->cs_open = c->cs_top_valid = false;
     c->stage = std::min(c->stage, 1);
     return RDF_OK;
 }
@@ -744,7 +757,7 @@ rdf_status rdf_set_triples(rdf_ctx* c, const uint32_t* s, const uint32_t* p, con
     c->n = n;
     c->V = num_terms;
     c->stage = 1;
-    c->paged = false;  // a paged run's state belongs to the previous input
+    c->paged = c->cs_open = c->cs_top_valid = false;  // a paged run's state belongs to the previous input
     c->parsed_dict = false;
     c->ingest_sharded = false;
     return RDF_OK;
@@ -763,7 +776,7 @@ rdf_status rdf_set_triples_device(rdf_ctx* c, const uint32_t* s, const uint32_t*
     c->n = n;
     c->V = num_terms;
     c->stage = 1;
-    c->paged = false;  // a paged run's state belongs to the previous input
+    c->paged = c->cs_open = c->cs_top_valid = false;  // a paged run's state belongs to the previous input
     c->parsed_dict = false;
     c->ingest_sharded = false;
     return RDF_OK;
@@ -815,7 +828,7 @@ rdf_status rdf_distinct_triples(rdf_ctx* c, uint64_t* n_distinct, float* ms) {
     if (ms) HIP_TRY(c, hipEventElapsedTime(ms, c->ev[6], c->ev[7]));
     c->n = kept;
     c->stage = 1;
-    c->paged = false;  // a paged run's state belongs to the previous input
+    c->paged = c->cs_open = c->cs_top_valid = false;  // a paged run's state belongs to the previous input
     if (n_distinct) *n_distinct = kept;
     return RDF_OK;
 }
@@ -927,7 +940,7 @@ rdf_status rdf_parse_ntriples(rdf_ctx* c, const char* text, uint64_t nbytes, uin
     c->n = n;
     c->V = (u32)V;
     c->stage = 1;
-    c->paged = false;  // a paged run's state belongs to the previous input
+    c->paged = c->cs_open = c->cs_top_valid = false;  // a paged run's state belongs to the previous input
     c->n_terms_parsed = V;
     c->parsed_dict = true;
     c->ingest_sharded = false;
@@ -1004,7 +1017,7 @@ rdf_status rdf_parse_begin(rdf_ctx* c, uint32_t flags, uint64_t reserve_triples)
     c->ntext.release();
     c->ntheap.release();
     c->stage = 0;
-    c->paged = false;
+    c->paged = c->cs_open = c->cs_top_valid = false;
     c->parsed_dict = false;
     c->dict_in_heap = false;
     c->ingest_sharded = false;
@@ -1196,7 +1209,7 @@ rdf_status rdf_parse_end(rdf_ctx* c, rdf_parse_stats* stats) {
     c->n = c->pc_n;
     c->V = (u32)c->pc_V;
     c->stage = 1;
-    c->paged = false;
+    c->paged = c->cs_open = c->cs_top_valid = false;
     c->n_terms_parsed = c->pc_V;
     c->parsed_dict = true;
     c->dict_in_heap = true;
@@ -1432,7 +1445,7 @@ rdf_status rdf_rewrite_terms(rdf_ctx* c, uint32_t flags, const char* key_heap, c
     c->p = c->tp.as<u32>();
     c->o = c->to.as<u32>();
     c->stage = 1;
-    c->paged = false;
+    c->paged = c->cs_open = c->cs_top_valid = false;
     return RDF_OK;
 }
 
@@ -1839,7 +1852,7 @@ static rdf_status fc_begin(rdf_ctx* c, uint32_t min_support) {
     c->ar_on = false;
     c->n_rules = 0;
     c->class_pending = false;
-    c->paged = false;
+    c->paged = c->cs_open = c->cs_top_valid = false;
     c->path_k1 = c->path_k2 = 0;
     for (int i = 0; i < RDF_NUM_TIMERS; ++i) c->tn[i] = 0;  // a failed run may have left segments behind
     c->pend_fc = c->pend_groups = c->pend_heavy = false;
@@ -2843,7 +2856,7 @@ rdf_status rdf_build_capture_groups(rdf_ctx* c, const char* projection, rdf_grou
     TRY(parse_projection(c, projection, &proj));
     c->rank = 0;
     c->nranks = 1;
-    c->paged = false;
+    c->paged = c->cs_open = c->cs_top_valid = false;
     c->n_group_ranges = 1;
     if (c->sw.group_range_records || 9 * c->n >= (1ull << 32)) {
         TRY(g_build_ranges(c, proj, c->sw.group_range_records ? c->sw.group_range_records : auto_range_records(c)));
@@ -3816,7 +3829,7 @@ rdf_status rdf_discover_cinds(rdf_ctx* c, uint32_t flags, rdf_cind_stats* stats)
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(hv_wait(c, true));
     c->res_bits = c->heavy_pending = false;  // (the heavy-bits form: results of d_emit_rest / d_page_emit only)
-    c->paged = false;
+    c->paged = c->cs_open = c->cs_top_valid = false;
     // test hook (RDFIND_TEST_OOM_DISCOVERY=1): the unpaged discovery reports RDF_ERR_OOM at once, so a caller's
     // fallback to pages runs on small inputs
     if (c->sw.test_oom_discovery) return fail(c, RDF_ERR_OOM, "test hook: the unpaged discovery runs out of memory");
@@ -4108,6 +4121,7 @@ rdf_status rdf_discover_cinds_paged(rdf_ctx* c, uint32_t flags, uint64_t page_by
     c->pg_pages = 0;
     c->pg_unary_done = false;
     c->paged = true;
+    c->cs_open = c->cs_top_valid = false;  // (a new capture table)
     HIP_TRY(c, hipEventRecord(c->ev[5], st));
     HIP_TRY(c, hipStreamSynchronize(st));
     HIP_TRY(c, hipEventElapsedTime(&c->stage_ms[2], c->ev[4], c->ev[5]));
@@ -5160,7 +5174,7 @@ static rdf_status sh_phase24(rdf_ctx* c, rdf_exchange* req) {
     c->parsed_dict = false;
     c->ingest_sharded = true;
     c->stage = 1;
-    c->paged = false;  // a paged run's state belongs to the previous input
+    c->paged = c->cs_open = c->cs_top_valid = false;  // a paged run's state belongs to the previous input
     memset(req, 0, sizeof(*req));
     req->op = RDF_X_DONE;
     c->sh_phase = 9;
@@ -5266,7 +5280,7 @@ rdf_status rdf_shard_begin(rdf_ctx* c, uint32_t rank, uint32_t nranks, uint32_t 
     c->x_imported = true;
     c->spare_x = false;  // (a run that failed between phases 14 and 1 left them marked)
     c->stage = std::min(c->stage, 1);
-    c->paged = false;
+    c->paged = c->cs_open = c->cs_top_valid = false;
     return RDF_OK;
 }
 
@@ -5286,7 +5300,7 @@ rdf_status rdf_shard_parse_begin(rdf_ctx* c, uint32_t rank, uint32_t nranks, con
     c->sh_phase = 20;
     c->x_imported = true;
     c->stage = 0;  // no usable triples until the global ids arrive
-    c->paged = false;
+    c->paged = c->cs_open = c->cs_top_valid = false;
     if (n_triples) *n_triples = n;
     return RDF_OK;
 }
@@ -6141,6 +6155,189 @@ rdf_status rdf_count_literals(rdf_ctx* c, uint64_t* n_literals, uint64_t* n_term
     }
     if (n_literals) *n_literals = lit;
     if (n_terms) *n_terms = V;
+    return RDF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Result statistics (cindstats.inl): rdf_cind_stats_begin / _add / _end, rdf_cind_histogram, rdf_copy_top_refs.
+// Accumulators of their own (cs*), the rows and the sort scratch in the dataset statistics' hg* buffers, timing events
+// of their own: no pipeline state changes, and a pending class part stays pending.
+
+// single GPU, like rdf_join_histogram: a sharded protocol under way, or its finished run
+static rdf_status cs_single_gpu(rdf_ctx* c, const char* what) {
+    if ((c->sh_phase >= 0 && c->sh_phase != 9) || (c->nranks > 1 && c->stage >= 3))
+        return fail(c, RDF_ERR_STATE, std::string(what) + " reads one GPU's result, not a sharded run's");
+    return RDF_OK;
+}
+
+// device time between two of the statistics' events, added to part `k` of the open accumulation (after a stream wait)
+static rdf_status cs_add_time(rdf_ctx* c, int k, hipEvent_t a, hipEvent_t b) {
+    float ms = 0;
+    HIP_TRY(c, hipEventElapsedTime(&ms, a, b));
+    c->cs_ms[k] += ms;
+    return RDF_OK;
+}
+
+rdf_status rdf_cind_stats_begin(rdf_ctx* c) {
+    if (!c) return RDF_ERR_ARG;
+    c->cs_open = false;
+    TRY(cs_single_gpu(c, "rdf_cind_stats_begin"));
+    if (c->stage < 4 && !(c->paged && c->stage >= 3))
+        return fail(c, RDF_ERR_STATE, "rdf_discover_cinds or rdf_discover_cinds_paged must be called first");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const u32 C = c->C;
+    ENSURE(c, csnref, std::max<u64>(C, 1) * 4);
+    ENSURE(c, csindeg, std::max<u64>(C, 1) * 4);
+    ENSURE(c, cscode, std::max<u64>(C, 1));
+    ENSURE(c, cscell, CS_SCALARS * 8);
+    HIP_TRY(c, hipMemsetAsync(c->csnref.p, 0, std::max<u64>(C, 1) * 4, st));
+    HIP_TRY(c, hipMemsetAsync(c->csindeg.p, 0, std::max<u64>(C, 1) * 4, st));
+    HIP_TRY(c, hipMemsetAsync(c->cscell.p, 0, CS_SCALARS * 8, st));
+    if (C)
+        hipLaunchKernelGGL(k_cs_codes, dim3(grid_for(C, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->fext.as<u32>(), C,
+                           c->V ? c->V : 1u, c->bkeys.as<u64>(), c->cscode.as<unsigned char>());
+    HIP_TRY(c, hipGetLastError());
+    c->cs_ms[0] = c->cs_ms[1] = c->cs_ms[2] = 0;
+    c->cs_open = true;
+    return RDF_OK;
+}
+
+rdf_status rdf_cind_stats_add(rdf_ctx* c) {
+    if (!c) return RDF_ERR_ARG;
+    TRY(cs_single_gpu(c, "rdf_cind_stats_add"));
+    if (!c->cs_open) return fail(c, RDF_ERR_STATE, "no open accumulation: rdf_cind_stats_begin comes first");
+    if (c->stage < 4) return fail(c, RDF_ERR_STATE, "no current result: rdf_next_page comes first");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    TRY(materialize_heavy(c));
+    // the rows that lie in `out` (class rows already expanded count as explicit) and their runs; a pending class part
+    // is counted from its compact form
+    const bool pending = c->class_pending && c->pend_NT;
+    const u64 nrows = c->class_pending ? c->n_out - c->n_class_out : c->n_out;
+    const u64 R = c->class_pending ? c->n_runs_explicit : c->n_runs;
+    u32* nref = c->csnref.as<u32>();
+    u32* indeg = c->csindeg.as<u32>();
+    const unsigned char* code = c->cscode.as<unsigned char>();
+    HIP_TRY(c, hipEventRecord(c->cs_ev[0], st));
+    if (nrows && R) {
+        hipLaunchKernelGGL(k_cs_run_refs, dim3(grid_for(R, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->runoff.as<u64>(),
+                           c->rundep.as<u32>(), R, nref);
+        hipLaunchKernelGGL(k_cs_explicit, dim3(grid_for(nrows, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->out_ptr, nrows,
+                           c->runoff.as<u64>(), c->rundep.as<u32>(), R, code, indeg, c->cscell.as<u64>());
+    }
+    HIP_TRY(c, hipEventRecord(c->cs_ev[1], st));
+    if (pending && c->n_classes)
+        hipLaunchKernelGGL(k_cs_class, dim3(vgrid(std::min<u64>(c->n_classes, kGrid))), dim3(RDF_BLOCK), 0, st,
+                           (u32)c->n_classes, c->coff.as<u64>(), c->cchoff.as<u64>(), c->lwoff.as<u64>(), c->clists.as<u32>(),
+                           c->ckeys.as<u64>(), c->cself.as<u32>(), c->cmcnt.as<u32>(), code, nref, indeg,
+                           c->cscell.as<u64>());
+    HIP_TRY(c, hipEventRecord(c->cs_ev[2], st));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+    TRY(cs_add_time(c, 0, c->cs_ev[0], c->cs_ev[1]));
+    return cs_add_time(c, 1, c->cs_ev[1], c->cs_ev[2]);
+}
+
+rdf_status rdf_cind_stats_end(rdf_ctx* c, uint64_t* n_rows, float* ms) {
+    if (!c) return RDF_ERR_ARG;
+    TRY(cs_single_gpu(c, "rdf_cind_stats_end"));
+    if (!c->cs_open) return fail(c, RDF_ERR_STATE, "no open accumulation: rdf_cind_stats_begin comes first");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    c->cs_open = c->cs_top_valid = false;
+    c->hist_valid = false;
+    const u32 C = c->C;
+    u64* cells = c->cscell.as<u64>();
+    HIP_TRY(c, hipEventRecord(c->cs_ev[0], st));
+    // kinds 3 and 4: one level-2 key per dependent and per capture, sorted, one row per run; the zero entries' run
+    // (kind CS_KIND_ZERO, the last one) is dropped
+    u64 R34 = 0, R2 = 0, nz[2] = {0, 0};
+    if (C) {
+        ENSURE(c, hgl, 2ull * C * 8);
+        ENSURE(c, hgl_tmp, 2ull * C * 8);
+        hipLaunchKernelGGL(k_cs_level2, dim3(grid_for(C, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->csnref.as<u32>(),
+                           c->csindeg.as<u32>(), C, c->hgl.as<u64>(), cells);
+        TRY(h_level2_rows(c, 2ull * C, 35, c->hgstage, 0, &R34));
+        TRY(read_multi(c, {{cells + CS_NZ, 8}, {cells + CS_NZ + 1, 8}}, nz));
+        if (nz[0] + nz[1] < 2ull * C) --R34;
+    }
+    // kind 2: the dependents with refs sorted by support, their refs summed per run of equal supports; the run of the
+    // dependents without refs (support NONE32, the last one) is dropped
+    if (nz[0]) {
+        ENSURE(c, hgk, (u64)C * 8);
+        ENSURE(c, hgk_tmp, (u64)C * 8);
+        ENSURE(c, cswsum, (C + 1ull) * 8);
+        const dim3 g(grid_for(C, RDF_BLOCK, kGrid));
+        hipLaunchKernelGGL(k_cs_support_keys, g, dim3(RDF_BLOCK), 0, st, c->csnref.as<u32>(), c->csup.as<u32>(), C,
+                           c->hgk.as<u64>());
+        TRY(h_sort(c, c->hgk, c->hgk_tmp, C, 64));
+        hipLaunchKernelGGL(k_cs_support_weights, g, dim3(RDF_BLOCK), 0, st, c->hgk.as<u64>(), (u64)C, c->csnref.as<u32>(),
+                           c->cswsum.as<u64>());
+        HIP_TRY(c, exclusive_scan_u64(c->ws, c->cswsum.as<u64>(), c->cswsum.as<u64>(), C, c->cswsum.as<u64>() + C, st));
+        TRY(h_run_starts(c, c->hgk.as<u64>(), C, 32, c->hgpos, &R2));
+        if (nz[0] < C) --R2;
+    }
+    // kind 1: the non-zero cells
+    u64 hcells[CS_CELLS];
+    HIP_TRY(c, ctx_copy(c, hcells, cells, sizeof(hcells), hipMemcpyDeviceToHost));
+    u64 R1 = 0;
+    for (u64 v : hcells) R1 += v ? 1 : 0;
+    const u64 rows = R1 + R2 + R34;
+    ENSURE(c, hgrows, std::max<u64>(rows, 1) * sizeof(rdf_hist_row));
+    rdf_hist_row* out = c->hgrows.as<rdf_hist_row>();
+    if (R1) hipLaunchKernelGGL(k_cs_shape_rows, dim3(1), dim3(RDF_WAVE), 0, st, cells, out);
+    if (R2)
+        hipLaunchKernelGGL(k_cs_support_rows, dim3(grid_for(R2, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->hgk.as<u64>(),
+                           c->hgstart.as<u32>(), R2, c->cswsum.as<u64>(), out + R1);
+    if (R34)
+        HIP_TRY(c, hipMemcpyAsync(out + R1 + R2, c->hgstage.p, R34 * sizeof(rdf_hist_row), hipMemcpyDeviceToDevice, st));
+    // the top list: the captures by descending in-degree, then ascending external id; the first nz[1] are referenced
+    if (C) {
+        ENSURE(c, cstop, (u64)C * 8);
+        ENSURE(c, cstop_tmp, (u64)C * 8);
+        hipLaunchKernelGGL(k_cs_top_keys, dim3(grid_for(C, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->csindeg.as<u32>(),
+                           c->fext.as<u32>(), C, c->cstop.as<u64>());
+        TRY(h_sort(c, c->cstop, c->cstop_tmp, C, 64));
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->cs_ev[1], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    TRY(cs_add_time(c, 2, c->cs_ev[0], c->cs_ev[1]));
+    c->cs_top_n = nz[1];
+    c->cs_top_valid = true;
+    c->hist_rows = rows;
+    c->hist_valid = true;
+    if (n_rows) *n_rows = rows;
+    if (ms) *ms = c->cs_ms[0] + c->cs_ms[1] + c->cs_ms[2];
+    return RDF_OK;
+}
+
+rdf_status rdf_cind_histogram(rdf_ctx* c, uint64_t* n_rows, float* ms) {
+    if (!c) return RDF_ERR_ARG;
+    if (c->stage < 4) {  // (begin alone also takes a prepared paged run, which has no current result yet)
+        TRY(cs_single_gpu(c, "rdf_cind_histogram"));
+        return fail(c, RDF_ERR_STATE, "rdf_discover_cinds must be called first");
+    }
+    TRY(rdf_cind_stats_begin(c));
+    TRY(rdf_cind_stats_add(c));
+    return rdf_cind_stats_end(c, n_rows, ms);
+}
+
+rdf_status rdf_copy_top_refs(rdf_ctx* c, rdf_top_ref* out, uint64_t cap, uint64_t* n_copied) {
+    if (!c || (cap && !out)) return RDF_ERR_ARG;
+    TRY(cs_single_gpu(c, "rdf_copy_top_refs"));
+    if (!c->cs_top_valid) return fail(c, RDF_ERR_STATE, "no top list: rdf_cind_stats_end or rdf_cind_histogram comes first");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const u64 m = std::min<u64>(cap, c->cs_top_n);
+    std::vector<u64> keys(m);
+    if (m) HIP_TRY(c, ctx_copy(c, keys.data(), c->cstop.p, m * 8, hipMemcpyDeviceToHost));
+    for (u64 i = 0; i < m; ++i) {
+        out[i].capture = (u32)keys[i];
+        out[i].pad = 0;
+        out[i].cinds = 0xffffffffu - (u32)(keys[i] >> 32);
+    }
+    if (n_copied) *n_copied = m;
     return RDF_OK;
 }
 

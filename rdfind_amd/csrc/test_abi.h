@@ -1,5 +1,6 @@
 /* Test-only entry points of librdfind_hip.so (rdf_test_*): the scan and radix primitives of primitives.hip on
- * caller-given data, and a report of the paths the last run took.  Not part of the product ABI
+ * caller-given data, a report of the paths the last run took, and the split timing of the result statistics.  Not part of
+ * the product ABI
  * (include/rdfind_hip.h): bound by rdfind_amd/_lib.py for tests/test_gpu_primitives.py and the forced-path tests.
  *
  * Every call runs on the context's stream with the context's workspace, touches no pipeline state (the stage and
@@ -92,6 +93,10 @@ rdf_status rdf_test_paths(rdf_ctx* ctx, rdf_test_path_report* out);
  * large for LDS).  0: no call yet, or the last one had no keys or no terms. */
 enum { RDF_TEST_RW_LDS = 1, RDF_TEST_RW_GLOBAL = 2 };
 rdf_status rdf_test_rewrite_form(rdf_ctx* ctx, uint32_t* form);
+
+/* Device time (ms) of the last result statistics (rdf_cind_stats_begin .. _end, rdf_cind_histogram), split:
+ * [0] the explicit passes of its add calls, [1] their class passes, [2] the end.  For tools/cindstats_bench.py. */
+rdf_status rdf_test_cind_stats_times(rdf_ctx* ctx, float* ms3);
 
 #ifdef __cplusplus
 }

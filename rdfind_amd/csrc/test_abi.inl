@@ -213,4 +213,10 @@ rdf_status rdf_test_rewrite_form(rdf_ctx* c, uint32_t* form) {
     return RDF_OK;
 }
 
+rdf_status rdf_test_cind_stats_times(rdf_ctx* c, float* ms3) {
+    if (!c || !ms3) return RDF_ERR_ARG;
+    for (int i = 0; i < 3; ++i) ms3[i] = c->cs_ms[i];
+    return RDF_OK;
+}
+
 }  // extern "C"

@@ -8,6 +8,9 @@ middle stages run on the GPU through the C ABI (``include/rdfind_hip.h``); there
 ``--host-parser`` the parse and the term rewrite run on the host instead (rdfind_amd/ntriples.py, same results).
 ``--create-join-histogram`` (RDFind.scala:449-452) prints the join-line sizes before the traversal
 (``rdf_join_histogram``, on the device); the reference's counting programs are ``python -m rdfind_amd.count``.
+``--cind-statistics [K]`` (build-specific) prints what the result contains before ``Detected n CINDs.``: the CINDs per
+shape and per support, the dependents per number of references, the captures per in-degree and the K most referenced
+captures (``rdf_cind_histogram`` / ``rdf_cind_stats_*``, on the device, the class part of the result unexpanded).
 
 Flag names follow ``RDFind.Parameters`` (RDFind.scala:639-721).  Flags that only change how Flink
 executes (and not the result) are accepted and ignored; flags whose semantics are out of scope for
@@ -72,6 +75,10 @@ def build_parser():
                     help="build-specific: discover the CINDs in pages of this much device working memory (0: "
                          "automatic), each page written before the next.  Without it a result larger than the device "
                          "memory switches to pages by itself")
+    ap.add_argument("--cind-statistics", type=int, nargs="?", const=10, default=None, metavar="K",
+                    help="build-specific: print the result's statistics before the CIND count: CINDs per shape and per "
+                         "support, dependents per number of references, captures per in-degree, and the K (default 10) "
+                         "most referenced captures")
     ap.add_argument("--ingest-window", type=int, default=1 << 30, metavar="BYTES",
                     help="build-specific: an input larger than this is parsed on the device in windows of whole lines "
                          "of at most this many bytes, so neither the host nor the GPU holds the whole text")
@@ -109,6 +116,10 @@ class RDFind:
         if self.args.create_join_histogram and self.args.dop > 1:
             # rdf_join_histogram reads one GPU's triples and frequent conditions; a rank holds a slice of either
             raise NotImplementedError("--create-join-histogram with -dop > 1")
+        if self.args.cind_statistics is not None and self.args.dop > 1:
+            # the result statistics read one GPU's result; a rank holds its own dependents only, and a capture's
+            # in-degree would need a collective over capture ids
+            raise NotImplementedError("--cind-statistics with -dop > 1")
         self.timings = {}
         self.rewrite_stats = None  # rdf_rewrite_stats of the device term rewrite (--prefixes / --asciify-triples)
 
@@ -139,6 +150,8 @@ class RDFind:
                 raise NotImplementedError("--find-only-fcs / --do-only-join with -dop > 1")
             if a.create_join_histogram:
                 raise NotImplementedError("--create-join-histogram with -dop > 1")
+            if a.cind_statistics is not None:
+                raise NotImplementedError("--cind-statistics with -dop > 1")
             import torch
             import torch.distributed as dist  # the ranks' exchange (rdfind_amd/distributed.py)
             if not dist.is_initialized():  # RDFIND_DIST_BACKEND=gloo: host-staged exchange (rehearsals on one GPU)
@@ -285,7 +298,10 @@ class RDFind:
         returned list.  With -dop > 1 every rank writes its own CINDs to a part file and rank 0 concatenates them
         into the one output file (the reference writes file:// outputs with parallelism 1, RDFind.scala:507-520).
         page_bytes (not None): the discovery runs now, page by page (rdf_discover_cinds_paged), and every page is
-        formatted and written before the next one is computed."""
+        formatted and written before the next one is computed.
+        --cind-statistics: taken before any formatting (unpaged), so the class part is counted unexpanded and a result
+        that is neither written nor kept as lines is never expanded; or accumulated page by page.  Printed to out
+        before the lines and the count."""
         a = self.args
         ctx.sync()
         self.timings["discover"] = time.time() - t1
@@ -306,20 +322,31 @@ class RDFind:
         if path:
             f = open(path if self.world == 1 else f"{path}.part{self.rank}", "wb")
         n = 0
+        stats_k = a.cind_statistics
+        stat_rows = top = None
         try:
             if page_bytes is None:
                 n = ctx.cind_count()
+                if stats_k is not None:
+                    stat_rows, top = ctx.cind_histogram(), ctx.top_refs(stats_k)
                 lines = lines if n <= KEEP_LINES_MAX or keep_all else None
                 self._format_result(ctx, n, f, lines)
             else:
                 pages = 0
-                for _ in ctx.pages(a.clean_implied, a.traversal_strategy, page_bytes):
+                ctx.discover_cinds_paged(a.clean_implied, a.traversal_strategy, page_bytes)
+                if stats_k is not None:
+                    ctx.cind_stats_begin()
+                while ctx.next_page() is not None:
+                    if stats_k is not None:
+                        ctx.cind_stats_add()
                     m = ctx.cind_count()
                     n += m
                     pages += 1
                     if lines is not None and n > KEEP_LINES_MAX and not keep_all:
                         lines = None
                     self._format_result(ctx, m, f, lines)
+                if stats_k is not None:
+                    stat_rows, top = ctx.cind_stats_end(), ctx.top_refs(stats_k)
                 self.stats["pages"] = pages
                 if a.debug_level >= 1:
                     self.log(f"{pages} pages.")
@@ -336,6 +363,9 @@ class RDFind:
             self.log(f"Found {n} CINDs in total.")
         if path:
             self.log(f"Outputting CINDs to {os.path.abspath(path)}.")
+        if stat_rows is not None:
+            for ln in cind_statistics_lines(stat_rows.tolist(), top.tolist(), *self._capture_lookup(ctx, top["capture"])):
+                print(ln, file=out)
         if a.collect_result or a.debug_level >= 3:
             for ln in lines:
                 print(ln, file=out)
@@ -343,6 +373,17 @@ class RDFind:
             print(f"Detected {n} CINDs.", file=out)
         self.n_cinds = n
         return lines
+
+    @staticmethod
+    def _capture_lookup(ctx, captures):
+        """(decode, term) for the given external capture ids: capture -> (code, value1, value2 or None) and term id ->
+        string, the terms read back from the formatting dictionary on the device (only those the captures name)."""
+        code, v1, v2 = _lib.decode_captures(np.asarray(captures, np.uint32), ctx.num_terms, ctx.binary_keys())
+        table = {int(c): (int(t), int(a), None if int(b) == codes.UINT32_NONE else int(b))
+                 for c, t, a, b in zip(captures, code, v1, v2)}
+        ids = sorted({v for _, a, b in table.values() for v in (a, b) if v is not None})
+        names = dict(zip(ids, ctx.dictionary_terms(ids))) if ids else {}
+        return table.__getitem__, names.__getitem__
 
     @staticmethod
     def _format_result(ctx, n, f, lines):
@@ -426,6 +467,37 @@ def format_rules(rules, term):
 def join_histogram_lines(rows):
     """--create-join-histogram's lines (RDFind.scala:451) of rdf_hist_row rows, ascending by join size."""
     return [f"Join size {k} encountered {t}x" for _, k, t in rows.tolist()]
+
+
+def shape_name(code):
+    """A capture code without its values: ``s[p]``, ``o[s,p]`` (ConditionCodes.prettyPrint's frame)."""
+    chars = {codes.SUBJECT: "s", codes.PREDICATE: "p", codes.OBJECT: "o"}
+    first, second, _ = codes.decode(codes.extract_primary(code))
+    cond = chars[first] + ("," + chars[second] if second else "")
+    return f"{chars[codes.extract_secondary(code)]}[{cond}]"
+
+
+def cind_statistics_lines(rows, top, decode, term):
+    """--cind-statistics' lines.  rows: (kind, value, times) as rdf_cind_histogram returns them, ascending by
+    (kind, value); top: (capture, cinds) in the order to print; decode(capture) -> (code, value1, value2 or None);
+    term(id) -> the term's string."""
+    out = []
+    for kind, value, times in rows:
+        if kind == _lib.RDF_CS_SHAPE:
+            out.append(f"CIND shape {shape_name(value >> 8)} < {shape_name(value & 0xFF)} encountered {times}x")
+        elif kind == _lib.RDF_CS_SUPPORT:
+            out.append(f"CIND support {value} encountered {times}x")
+        elif kind == _lib.RDF_CS_REFS:
+            out.append(f"Dependents with {value} references encountered {times}x")
+        elif kind == _lib.RDF_CS_INDEGREE:
+            out.append(f"Captures referenced {value} times encountered {times}x")
+        else:
+            raise ValueError(f"unknown statistics row kind {kind}")
+    for capture, cinds in top:
+        code, v1, v2 = decode(capture)
+        out.append(f"Most referenced: {codes.pretty_print(code, term(v1), None if v2 is None else term(v2))} "
+                   f"by {cinds} CINDs")
+    return out
 
 
 def format_rows(rows, term):
