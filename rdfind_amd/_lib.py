@@ -46,8 +46,8 @@ RDF_RW_ASCIIFY = 1
 RDF_NT_TABS = 1
 
 # the test-only entry points of rdfind_amd/csrc/test_abi.h (not part of the product ABI)
-TEST_SYMBOLS = ("rdf_test_scan", "rdf_test_scan_batch", "rdf_test_radix", "rdf_test_radix_passes", "rdf_test_paths",
-                "rdf_test_rewrite_form", "rdf_test_cind_stats_times")
+TEST_SYMBOLS = ("rdf_test_scan", "rdf_test_scan_batch", "rdf_test_radix", "rdf_test_radix_passes",
+                "rdf_test_radix_segments", "rdf_test_paths", "rdf_test_rewrite_form", "rdf_test_cind_stats_times")
 REWRITE_FORMS = {0: None, 1: "lds", 2: "global"}
 SCAN_U32_U32, SCAN_U32_U64, SCAN_U64_U64 = range(3)
 SCAN_DTYPES = {SCAN_U32_U32: (np.uint32, np.uint32), SCAN_U32_U64: (np.uint32, np.uint64),
@@ -113,7 +113,7 @@ class PathReport(ctypes.Structure):
                 ("n_light_survivors", ctypes.c_uint64),
                 ("light_npx", ctypes.c_uint32), ("packed_npx", ctypes.c_uint32), ("light_ordered", ctypes.c_uint32),
                 ("light_side", ctypes.c_uint32), ("light_two_pass", ctypes.c_uint32), ("sig_on", ctypes.c_uint32),
-                ("piv2_on", ctypes.c_uint32)]
+                ("piv2_on", ctypes.c_uint32), ("k3_hist", ctypes.c_uint32)]
 
 
 class ResultLayout(ctypes.Structure):
@@ -262,6 +262,8 @@ def load():
         "rdf_test_radix": (i32, [P, ctypes.c_int, P, u64, ctypes.c_int, ctypes.c_int, u64, P, ctypes.POINTER(u64),
                                  ctypes.POINTER(u32)]),
         "rdf_test_radix_passes": (ctypes.c_int, [ctypes.c_int]),
+        "rdf_test_radix_segments": (i32, [P, P, u64, P, u64, P, u32, ctypes.c_int, ctypes.c_int, ctypes.c_int32, u32, u32,
+                                          P, ctypes.POINTER(u64), ctypes.POINTER(u32)]),
         "rdf_test_paths": (i32, [P, ctypes.POINTER(PathReport)]),
         "rdf_test_rewrite_form": (i32, [P, ctypes.POINTER(u32)]),
         "rdf_test_cind_stats_times": (i32, [P, ctypes.POINTER(ctypes.c_float)]),
@@ -691,19 +693,39 @@ class Context:
         self._check(rc, "rdf_test_radix")
         return out[: n_out.value], bool(ok.value)
 
+    def test_radix_segments(self, src, counts, bases=None, stride=0, w0=0, bits=64, bump=None):
+        """The sort of the keys that lie in segments of ``src`` (rdf_test_radix_segments): segment b is ``counts[b]``
+        keys from ``bases[b]`` (``bases`` None: from ``b * stride``).  ``w0``: the first digit's width (0: the sort's
+        own).  ``bump`` = (segment, digit, delta) changes one entry of the histogram the first pass is given.  Returns
+        (sorted keys, canaries_ok)."""
+        a = np.ascontiguousarray(src, dtype=np.uint64)
+        cnt = np.ascontiguousarray(counts, dtype=np.uint64)
+        base = None if bases is None else np.ascontiguousarray(bases, dtype=np.uint64)
+        assert base is None or base.shape == cnt.shape
+        out = np.empty(max(int(cnt.sum()), 1), np.uint64)
+        bseg, bdig, bdelta = bump if bump else (0, 0, 0)
+        n_out, ok = ctypes.c_uint64(), ctypes.c_uint32()
+        rc = self._test_fn("rdf_test_radix_segments")(
+            self.ptr, a.ctypes.data, a.shape[0], None if base is None else base.ctypes.data, stride, cnt.ctypes.data,
+            cnt.shape[0], w0, bits, bdelta, bseg, bdig, out.ctypes.data, ctypes.byref(n_out), ctypes.byref(ok))
+        self.test_canaries_ok = bool(ok.value)
+        self._check(rc, "rdf_test_radix_segments")
+        return out[: n_out.value], bool(ok.value)
+
     def test_paths(self) -> dict:
         """Which alternative paths the last completed run took (rdf_test_paths): the K1 / K2 / K3 forms by name,
         dense_on, light_stage, light_hiocc, n_dense, n_dense_eligible, n_dedup_members, and what the light launches
         were given, summed over the run's pages, ranges and light passes: n_light_items (k_light work items),
         n_packed_octets (k_light_packed), n_mseg_chunks (k_light_mseg_emit), n_multi_items (items of dependents with
         several chunks), n_light_survivors (pass B's input), light_npx / packed_npx (extra pivots checked), and the
-        flags light_ordered, light_side, light_two_pass, sig_on, piv2_on."""
+        flags light_ordered, light_side, light_two_pass, sig_on, piv2_on, k3_hist (K3 handed the record sort its first
+        digit histogram)."""
         r = PathReport()
         self._check(self._test_fn("rdf_test_paths")(self.ptr, ctypes.byref(r)), "rdf_test_paths")
         d = _struct_dict(r)
         d["k1_form"], d["k2_form"], d["k3_form"] = K1_FORMS[r.k1_form], K2_FORMS[r.k2_form], K3_FORMS[r.k3_form]
         for name in ("dense_on", "light_stage", "light_hiocc", "light_ordered", "light_side", "light_two_pass", "sig_on",
-                     "piv2_on"):
+                     "piv2_on", "k3_hist"):
             d[name] = bool(d[name])
         return d
 

@@ -525,15 +525,34 @@ __device__ inline u32 triple_records(u64 i, const u32* __restrict__ s, const u32
 // emission (a join range's second emission reusing its first's scanned offsets) cannot write past the buffer; a record
 // that does not fit sets *block_counts (the overflow word of the write pass) and the host fails the build with
 // RDF_ERR_LIMIT (g_emit_range)
-template <bool WRITE, bool LAZY>
+// HIST (region mode only): the block also counts the record sort's first digit (record bits [0, w0), the low join
+// bits) of its kept records and writes column blockIdx.x of the digit-major histogram hist[d * hstride + block] at its
+// end, and adds its kept count to block_counts[gridDim.x + 1]: the sort's first pass then scatters straight from the
+// regions (radix_seg_first_pass), with no compaction, no scan of the block counts and no count pass.  A triple's records
+// share at most three join values (the object's, the predicate's, the subject's records are consecutive), so a lane
+// counts three weighted digits per iteration, not nine records, each by one LDS atomic into its wave's own row of
+// counters.  Records joined on the predicate put a wave's records into a few bins; counting them by wave ballots as
+// k_radix_count does (one leader lane per digit adds its peers' sum) avoids that serialisation but measured slower here
+// (c2 emit 0.528 ms all by ballots, 0.495 the predicate's only, 0.483 all by atomics;
+// profiles/emit_hist_variants_ab.log).  Where the digit is wider than the join value (inputs of a few hundred terms) it
+// reaches into the capture, and the records are counted one by one.
+template <bool WRITE, bool LAZY, bool HIST = false>
 __global__ __launch_bounds__(RDF_BLOCK) void k_emit_records(const u32* __restrict__ s, const u32* __restrict__ p,
                                                             const u32* __restrict__ o, u64 n, u64 per, u32 V, u32 twoU,
                                                             const u32* __restrict__ frank, const u64* __restrict__ lkeys,
                                                             const u32* __restrict__ lvals, u64 lmask, int proj,
                                                             int joinbits, JoinSel js, u64* block_counts,
-                                                            const u64* __restrict__ block_offsets, u64* out, int recbits) {
+                                                            const u64* __restrict__ block_offsets, u64* out, int recbits,
+                                                            u32* __restrict__ hist = nullptr, u32 hstride = 0, int w0 = 0) {
+    static_assert(!HIST || WRITE, "the histogram belongs to the write pass");
+    constexpr u32 HBIN = 1u << RS_MAX_BITS;
     __shared__ u32 lds_wave[RDF_WAVES_PER_BLOCK];
     __shared__ u64 htab[WRITE ? EMIT_DEDUP_SLOTS : 1];  // the iteration's distinct records (write pass)
+    __shared__ u32 whist[HIST ? RDF_WAVES_PER_BLOCK * HBIN : 1];  // per-wave counters of the first sort digit
+    if (HIST) {
+        for (u32 k = threadIdx.x; k < RDF_WAVES_PER_BLOCK * HBIN; k += RDF_BLOCK) whist[k] = 0;
+        __syncthreads();
+    }
     const u64 b = (u64)blockIdx.x * per;
     const u64 e = b + per < n ? b + per : n;
     if (!WRITE) {  // the block's record count: per-thread sums, one block reduction at the end
@@ -567,8 +586,11 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_emit_records(const u32* __restric
     for (u64 i0 = b; i0 < e; i0 += RDF_BLOCK) {
         const u64 i = i0 + threadIdx.x;
         u64 rec[9];
-        u32 c = 0, rep = 0;
-        if (i < e) c = triple_records<LAZY>(i, s, p, o, V, twoU, frank, lkeys, lvals, lmask, proj, joinbits, js, rec, &rep);
+        u32 c = 0, rep = 0, grp = 0;
+        if (i < e)
+            c = triple_records<LAZY>(i, s, p, o, V, twoU, frank, lkeys, lvals, lmask, proj, joinbits, js, rec, &rep,
+                                     HIST ? &grp : nullptr);
+        if (HIST) rep |= grp << 16;  // (one register across the table lookups: the write pass's occupancy step)
         // Records repeated within the iteration's 256 triples (the same subject's predicate, the same (predicate,
         // object) pair: ~23 % of c2's records; only the kinds flagged by triple_records are looked up) are written
         // once; the count pass's region stays as it is and its tail is padded with EMIT_PAD, which the record sort's
@@ -608,6 +630,26 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_emit_records(const u32* __restric
                 }
             }
         }
+        if (HIST) {  // the kept records' first sort digits: one weighted LDS atomic per join attribute
+            const u32 dmask = (1u << w0) - 1u, co = (rep >> 16) & 3u, cop = co + ((rep >> 18) & 3u);
+            u32* mine = whist + (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / RDF_WAVE)) * HBIN;
+            if (w0 > joinbits) {  // a small input's digit reaches into the capture bits: record by record
+#pragma unroll
+                for (int k = 0; k < 9; ++k)
+                    if ((keep >> k) & 1u) atomicAdd(&mine[(u32)rec[k] & dmask], 1u);
+            } else {
+#pragma unroll
+                for (int g = 0; g < 3; ++g) {  // the records [lo, hi) joined on the object, the predicate, the subject
+                    const u32 lo = g == 0 ? 0u : g == 1 ? co : cop, hi = g == 0 ? co : g == 1 ? cop : c;
+                    const u32 wgt = (u32)__popc(keep & ((1u << hi) - (1u << lo)));
+                    u32 d = 0;
+#pragma unroll
+                    for (int k = 0; k < 9; ++k)
+                        if ((u32)k == lo && lo < hi) d = (u32)rec[k] & dmask;
+                    if (wgt) atomicAdd(&mine[d], wgt);
+                }
+            }
+        }
         // one scan of (kept, emitted) packed in 16-bit halves (each <= 9 x 256): this thread's kept records go to the
         // front of the iteration's region, its dropped ones become padding behind all kept records
         const u32 nk = (u32)__popc(keep);
@@ -637,6 +679,16 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_emit_records(const u32* __restric
     if (region && threadIdx.x == 0) {
         block_counts[blockIdx.x] = run - rbase;
         atomicAdd((unsigned long long*)(block_counts + gridDim.x), (unsigned long long)emitted);
+        if (HIST) atomicAdd((unsigned long long*)(block_counts + gridDim.x + 1), (unsigned long long)(run - rbase));
+    }
+    if (HIST) {
+        __syncthreads();
+        for (u32 d = threadIdx.x; d < (1u << w0); d += RDF_BLOCK) {
+            u32 sum = 0;
+#pragma unroll
+            for (int ww = 0; ww < RDF_WAVES_PER_BLOCK; ++ww) sum += whist[ww * HBIN + d];
+            hist[(u64)d * hstride + blockIdx.x] = sum;
+        }
     }
     if (!region && over) atomicOr((unsigned long long*)block_counts, 1ull);
 }

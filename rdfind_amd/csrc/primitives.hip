@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "primitives.hpp"
+#include "radix_host.hpp"
 #include "switches.hpp"
 
 namespace rdf {
@@ -655,6 +656,159 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_radix_scatter(const KT* __restric
     }
 }
 
+// First pass of a sort whose producer kept the digit histogram: the input is a list of segments (segment b: cnt[b] keys
+// from src + base[b], or from src + b * stride when base is null; disjoint, any length), one block a segment and column b
+// of the digit-major histogram that segment's counts.  The block walks its segment in sub-tiles of RS_TILE, ranks and
+// reorders each in LDS like k_radix_scatter, and carries every digit's output position from one sub-tile to the next
+// (gbase[d] += the sub-tile's count of d): the output is the LSD pass's with tile = segment, so it is stable.
+// Every access is bounded: a key at or past src_n is not read, a position at or past n_out not written, and either
+// sets *overflow, and so does a segment whose keys of some digit are not as many as its histogram column says (a
+// histogram that disagrees with its keys ends as the caller's error, never as a write past the buffer; n_out may
+// therefore be the buffer's capacity when the caller does not know the keys' number yet).
+template <int DB>
+__global__ __launch_bounds__(RDF_BLOCK) void k_radix_scatter_seg(const u64* __restrict__ src, u64 src_n,
+                                                                 u64* __restrict__ out, u64 n_out,
+                                                                 const u64* __restrict__ base, u64 stride,
+                                                                 const u64* __restrict__ cnt, int w,
+                                                                 const u32* __restrict__ offs,
+                                                                 const u32* __restrict__ rowtot, u32 row_stride,
+                                                                 u32* overflow) {
+    constexpr u32 NBIN = 1u << DB;
+    constexpr u32 PER = NBIN / RDF_BLOCK;
+    static_assert(NBIN % RDF_BLOCK == 0, "digit bins must be a multiple of the block");
+    __shared__ u64 skeys[RS_TILE];
+    __shared__ u32 wcount[RDF_WAVES_PER_BLOCK][NBIN];
+    __shared__ u32 tstart[NBIN];
+    __shared__ u32 gbase[NBIN];
+    __shared__ u32 gwant[NBIN];  // keys of the digit the histogram still expects from this segment
+    __shared__ u32 lds_wave[RDF_WAVES_PER_BLOCK];
+    __shared__ u32 s_tvalid;
+    const int lane = lane_id();
+    const int wave = threadIdx.x / RDF_WAVE;
+    const u32 nbin = 1u << w, dmask = nbin - 1u;
+    const u32 seg = rs_tile(), columns = gridDim.x;
+    const u64 sbase = base ? base[seg] : (u64)seg * stride;
+    const u64 sn = cnt[seg];
+    {   // the digits' bases (exclusive scan of the row totals) + this segment's row prefixes
+        u32 rt[PER], ro[PER], local = 0;
+#pragma unroll
+        for (u32 q = 0; q < PER; ++q) {
+            const u32 dg = threadIdx.x * PER + q;
+            rt[q] = dg < nbin ? rowtot[dg] : 0u;
+            ro[q] = dg < nbin ? offs[(u64)dg * row_stride + seg] : 0u;
+            local += rt[q];
+        }
+        u32 total;
+        u32 off = block_exclusive_scan<u32>(local, lds_wave, &total);
+#pragma unroll
+        for (u32 q = 0; q < PER; ++q) {
+            gbase[threadIdx.x * PER + q] = off + ro[q];
+            off += rt[q];
+            // this segment's keys of the digit, by the histogram (the next column's prefix, or the row's total)
+            const u32 dg = threadIdx.x * PER + q;
+            const u32 nx = dg >= nbin ? 0u : seg + 1 < columns ? offs[(u64)dg * row_stride + seg + 1] : rt[q];
+            gwant[dg] = nx - ro[q];
+        }
+    }
+    const u64 lt = lanemask_lt();
+    bool over = false;
+    for (u64 t0 = 0; t0 < sn; t0 += RS_TILE) {  // (the previous sub-tile ended with a barrier)
+        const u32 tn = sn - t0 < (u64)RS_TILE ? (u32)(sn - t0) : (u32)RS_TILE;
+        // A short last sub-tile is split evenly over the waves (rows of 64 keys each, wave-major like a full tile, so the
+        // order stays): c2's segments average 5.6k keys, and a 1.5k-key tail ranked as 16 rows by one wave cost as much as
+        // a full tile
+#ifndef RDF_SEG_BALANCE
+#define RDF_SEG_BALANCE 1
+#endif
+        const u32 rows = RDF_SEG_BALANCE ? (tn + RDF_BLOCK - 1) / RDF_BLOCK : (u32)RS_ITEMS;
+        const u32 wofs = (u32)wave * rows * RDF_WAVE;
+        for (u32 i = threadIdx.x; i < RDF_WAVES_PER_BLOCK * NBIN; i += RDF_BLOCK) (&wcount[0][0])[i] = 0;
+        // each wave loads its contiguous keys, 8 bytes a lane (a segment starts at any key, so no 16-byte loads)
+        u64 k[RS_ITEMS];
+        bool valid[RS_ITEMS];
+#pragma unroll
+        for (int r = 0; r < RS_ITEMS; ++r) {
+            const u32 p = wofs + (u32)r * RDF_WAVE + lane;
+            const u64 idx = sbase + t0 + p;
+            valid[r] = (u32)r < rows && p < tn && idx < src_n;
+            if ((u32)r < rows && p < tn && idx >= src_n) over = true;
+            k[r] = valid[r] ? src[idx] : 0ull;
+        }
+        __syncthreads();
+        u32 rank[RS_ITEMS];
+#pragma unroll
+        for (int r = 0; r < RS_ITEMS; ++r) {
+            if ((u32)r >= rows) {  // (block-uniform)
+                rank[r] = 0;
+                continue;
+            }
+            const u32 d = (u32)k[r] & dmask;
+            const u64 peers = digit_peers<DB>(d, valid[r]);
+            const u32 before = (u32)__popcll(peers & lt);
+            const u32 old = valid[r] ? wcount[wave][d] : 0;
+            if (valid[r] && ((peers >> lane) >> 1) == 0) wcount[wave][d] = old + before + 1;
+            rank[r] = old + before;
+        }
+        __syncthreads();
+        u32 run[PER], local = 0;
+#pragma unroll
+        for (u32 q = 0; q < PER; ++q) {
+            const u32 dg = threadIdx.x * PER + q;
+            u32 acc = 0;
+#pragma unroll
+            for (int ww = 0; ww < RDF_WAVES_PER_BLOCK; ++ww) {
+                const u32 c = wcount[ww][dg];
+                wcount[ww][dg] = acc;
+                acc += c;
+            }
+            run[q] = acc;
+            local += acc;
+        }
+        {
+            u32 total;
+            u32 off = block_exclusive_scan<u32>(local, lds_wave, &total);
+#pragma unroll
+            for (u32 q = 0; q < PER; ++q) {
+                tstart[threadIdx.x * PER + q] = off;
+                off += run[q];
+            }
+            if (threadIdx.x == 0) s_tvalid = total;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < RS_ITEMS; ++r) {
+            if (valid[r]) {
+                const u32 d = (u32)k[r] & dmask;
+                skeys[tstart[d] + wcount[wave][d] + rank[r]] = k[r];
+            }
+        }
+        __syncthreads();
+        const u32 tv = s_tvalid;
+#pragma unroll
+        for (int i = 0; i < RS_ITEMS; ++i) {
+            const u32 p = (u32)i * RDF_BLOCK + threadIdx.x;
+            if (p < tv) {
+                const u64 key = skeys[p];
+                const u32 d = (u32)key & dmask;
+                const u64 pos = (u64)gbase[d] + (p - tstart[d]);
+                if (pos < n_out) out[pos] = key;
+                else over = true;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (u32 q = 0; q < PER; ++q) {  // (read again after the next barriers; each thread its own digits)
+            gbase[threadIdx.x * PER + q] += run[q];
+            gwant[threadIdx.x * PER + q] -= run[q];
+        }
+    }
+    // the segment held exactly the histogram's keys of every digit: with that, the segments' runs tile dst[0, total)
+#pragma unroll
+    for (u32 q = 0; q < PER; ++q)
+        if (gwant[threadIdx.x * PER + q] != 0u) over = true;
+    if (over) atomicOr(overflow, 1u);
+}
+
 // The digit-major histogram's rows scanned in place, one 1024-thread block per digit (exclusive within the row: the
 // digit's keys in earlier tiles; c2's rows of 14.4k tiles in one step), each row's total to rowtot[digit].  The scatter
 // blocks scan the totals into the digits' bases themselves (a few hundred L2 loads, issued behind the tile's key
@@ -716,7 +870,7 @@ __global__ __launch_bounds__(RS_SCAN_THREADS) void k_radix_rowscan(u32* __restri
     if (threadIdx.x == 0) rowtot[blockIdx.x] = carry;
 }
 
-static inline u32 hist_stride(u32 tiles) { return (tiles + 3u) & ~3u; }
+static inline u32 hist_stride(u32 tiles) { return radix_hist_stride(tiles); }
 template <int DB, bool HASH = false, typename KT = u64>
 static hipError_t radix_pass(Workspace& ws, const KT* keys, KT* tmp, u64 n, int shift, int w, u32* hist, u32 tiles,
                              hipStream_t st, u32* d_kept = nullptr, u64 hmask = 0) {
@@ -739,8 +893,7 @@ static hipError_t radix_sort_dmax(Workspace& ws, u64*& keys, u64*& tmp, u64 n, i
 static int sort_digit_bits(int) { return RS_MAX_BITS; }
 
 int radix_sort_passes(int bits) {
-    const int d = sort_digit_bits(bits);
-    return bits > 0 ? (bits + d - 1) / d : 0;
+    return radix_passes_for(bits, sort_digit_bits(bits));
 }
 
 // Sort of keys some of which are padding (~0): the first pass drops them, *n_out (host) = the other keys, which the
@@ -767,6 +920,44 @@ hipError_t radix_sort_u64_drop(Workspace& ws, u64*& keys, u64*& tmp, u64 n, int 
     std::swap(keys, tmp);
     *n_out = kept;
     return radix_sort_dmax(ws, keys, tmp, kept, w0, bits, dmax, st);
+}
+
+// A sort of `bits` key bits whose first pass runs over the producer's segments (radix_seg_first_pass): the first
+// digit's width, the same one radix_sort_u64_drop takes, so the whole sort keeps its widths (43 bits: 9+9+9+8+8)
+int radix_first_width(int bits) {
+    return radix_pass_width(bits, sort_digit_bits(bits), 0);
+}
+u32 radix_seg_stride(u32 columns) { return hist_stride(columns); }
+// the workspace's histogram buffer for `columns` segments and a first digit of w bits: digit d's row starts at
+// d * radix_seg_stride(columns), column b is segment b's.  Valid until the next radix call on this workspace.
+u32* radix_seg_hist(Workspace& ws, u32 columns, int w) {
+    if (w < 1 || w > RS_MAX_BITS || columns == 0) return nullptr;
+    return (u32*)ws.scratch(((u64)hist_stride(columns) << w) * sizeof(u32), 1);
+}
+// rowscan of hist + the segment scatter of the low w bits: src's segments -> dst[0, n_out), stable.  *d_overflow (device,
+// zeroed by the caller) is set when the histogram and the keys disagree; dst then holds no sorted result.
+hipError_t radix_seg_first_pass(Workspace& ws, const u64* src, u64 src_n, u64* dst, u64 n_out, const u64* base, u64 stride,
+                                const u64* cnt, u32 columns, int w, u32* hist, u32* d_overflow, hipStream_t st) {
+    if (w < 1 || w > RS_MAX_BITS || columns == 0 || !hist || !d_overflow || !cnt) return hipErrorInvalidValue;
+    if (n_out >= (1ull << 32)) return hipErrorInvalidValue;
+    u32* rowtot = (u32*)ws.scratch(1024 * sizeof(u32), 2);
+    if (!rowtot) return hipErrorOutOfMemory;
+    const u32 rs = hist_stride(columns);
+    hipLaunchKernelGGL(k_radix_rowscan, dim3(1u << w), dim3(RS_SCAN_THREADS), 0, st, hist, rs, columns, rowtot);
+    if (w <= 8)
+        hipLaunchKernelGGL(k_radix_scatter_seg<8>, dim3(columns), dim3(RDF_BLOCK), 0, st, src, src_n, dst, n_out, base, stride,
+                           cnt, w, hist, rowtot, rs, d_overflow);
+    else if (w == 9)
+        hipLaunchKernelGGL(k_radix_scatter_seg<9>, dim3(columns), dim3(RDF_BLOCK), 0, st, src, src_n, dst, n_out, base, stride,
+                           cnt, w, hist, rowtot, rs, d_overflow);
+    else
+        hipLaunchKernelGGL(k_radix_scatter_seg<10>, dim3(columns), dim3(RDF_BLOCK), 0, st, src, src_n, dst, n_out, base, stride,
+                           cnt, w, hist, rowtot, rs, d_overflow);
+    return hipGetLastError();
+}
+// the passes after the first one: bits [w0, bits) of n keys, as radix_sort_u64_drop runs them
+hipError_t radix_sort_u64_rest(Workspace& ws, u64*& keys, u64*& tmp, u64 n, int w0, int bits, hipStream_t st) {
+    return radix_sort_dmax(ws, keys, tmp, n, w0, bits, sort_digit_bits(bits), st);
 }
 
 // Passes of at most RS_MAX_BITS bits (10 when that saves a pass), as even as possible (43 bits: 9+9+9+8+8 instead of

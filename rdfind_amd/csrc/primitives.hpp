@@ -99,6 +99,18 @@ static_assert(RS_MAX_BITS >= 8 && RS_MAX_BITS <= 10, "digit kernels exist for 8,
 hipError_t radix_sort_u64_drop(Workspace& ws, u64*& keys, u64*& tmp, u64 n, int bits, u32* d_kept, u64* n_out,
                                hipStream_t st);
 hipError_t radix_sort_u64_bits(Workspace& ws, u64*& keys, u64*& tmp, u64 n, int lo, int hi, hipStream_t st);
+// A sort whose producer hands over the first digit's histogram (K3's emission blocks): the keys lie in `columns`
+// disjoint segments of src (segment b: cnt[b] keys from base[b], or from b * stride when base is null) and
+// hist[d * radix_seg_stride(columns) + b] = segment b's keys with low w-bit digit d.  radix_seg_first_pass = rowscan +
+// one stable scatter of the segments into dst[0, n_out), no count pass and no compaction; radix_sort_u64_rest sorts the
+// remaining bits [w0, bits).  A histogram that disagrees with the keys sets *d_overflow; nothing is read past src_n or
+// written past n_out.  Uses workspace slots 1 (the histogram) and 2.
+int radix_first_width(int bits);  // the first digit's width of a sort of `bits` key bits
+u32 radix_seg_stride(u32 columns);
+u32* radix_seg_hist(Workspace& ws, u32 columns, int w);
+hipError_t radix_seg_first_pass(Workspace& ws, const u64* src, u64 src_n, u64* dst, u64 n_out, const u64* base, u64 stride,
+                                const u64* cnt, u32 columns, int w, u32* hist, u32* d_overflow, hipStream_t st);
+hipError_t radix_sort_u64_rest(Workspace& ws, u64*& keys, u64*& tmp, u64 n, int w0, int bits, hipStream_t st);
 int radix_sort_passes(int bits);  // passes of a sort of `bits` key bits
 hipError_t radix_partition_hashed(Workspace& ws, u64*& keys, u64*& tmp, u64 n, int bits, u64 hmask, hipStream_t st);
 // u32 keys ordered by bits [lo, hi) (stable LSD passes of <= 8 bits); keys / tmp swap so that `keys` holds the result

@@ -14,6 +14,7 @@
 #include "../../include/rdfind_hip.h"
 #include "test_abi.h"
 #include "primitives.hpp"
+#include "radix_host.hpp"
 #include "kernels.inl"
 #include "switches.hpp"
 
@@ -269,6 +270,8 @@ struct rdf_ctx : CtxBuffers {
     u64 n_dense_eligible = 0;             // groups d_dense_flags numbered (n_dense: the rows d_dense_build gave a bitmap)
     // which alternative ran at the run's decision points (RDF_TEST_K1_* / K2_* / K3_*, test_abi.h; 0: none yet)
     u32 path_k1 = 0, path_k2 = 0, path_k3 = 0;
+    // the last group build's K3 handed the record sort its first digit histogram (RDFIND_EMIT_HIST)
+    bool k3_hist = false;
     // what the light launches of the last discovery were given (d_light_kernels; sums over its pages, ranges and
     // passes), for rdf_test_paths
     struct LightPaths {
@@ -2048,6 +2051,7 @@ static rdf_status g_record_bits(rdf_ctx* c) {
     c->dense_on = false;
     c->n_dense = c->n_dense_eligible = c->n_dedup_members = 0;
     c->path_k3 = 0;
+    c->k3_hist = false;
     const u32 V = c->V ? c->V : 1;
     const u64 ncap = 2ull * c->U + c->B;  // compact candidate captures (k_frank_final)
     const int capbits = bits_for(ncap ? ncap - 1 : 0);
@@ -2091,6 +2095,7 @@ static const unsigned kEmitGrid = RDF_EMIT_GRID;
 static const unsigned kRangeEmitGrid = RDF_RANGE_EMIT_GRID;
 static constexpr u64 ECACHE_STRIDE = RDF_EMIT_GRID + 1ull;
 static rdf_status g_sort_support(rdf_ctx* c, u64* keys, u64* tmp, u64 Je, u32* sup, u64* Jout, u64* keep_out);
+static rdf_status g_support_sorted(rdf_ctx* c, u64* keys, u64 J, u32* sup, u64* Jout);
 static rdf_status g_emit_range(rdf_ctx* c, int proj, JoinSel js, u64 cap_rec, u32* sup, u64* Jout, int cache = 0) {
     hipStream_t st = c->stream;
     const u64 n = c->n;
@@ -2105,9 +2110,10 @@ static rdf_status g_emit_range(rdf_ctx* c, int proj, JoinSel js, u64 cap_rec, u3
     const int slot = cache > 0 ? cache - 1 : cache < 0 ? -cache - 1 : -1;
     // the selection takes a part of the join values (a join range, or a rank's shard): lazy condition-rank loads
     const bool lazy = js.nranks > 1 || js.lo != 0u || js.hi != JOIN_ALL_HI;
-    const unsigned eg = grid_for(n, RDF_BLOCK, kEmitGrid);
+    const unsigned eg =
+        grid_for(n, RDF_BLOCK, c->sw.emit_grid ? (unsigned)std::min<u64>(c->sw.emit_grid, kEmitGrid) : kEmitGrid);
     const u64 per = n ? (n + eg - 1) / eg : 0;
-    ENSURE(c, eblk, 2 * (eg + 1ull) * 8);
+    ENSURE(c, eblk, 2 * (eg + 2ull) * 8);
     const bool reuse = cache < 0 && slot < (int)c->ecache_je.size();
     u64* overflow = (u64*)dscal(c, 8);  // the write pass's overflow word (zeroed above)
     // one pass (no count pass) when the record buffers hold 9 records per triple: every block writes its kept records
@@ -2116,6 +2122,49 @@ static rdf_status g_emit_range(rdf_ctx* c, int proj, JoinSel js, u64 cap_rec, u3
     // (profiles/r05_emit_onepass_ab.log).  RDFIND_EMIT_ONEPASS=0: the count pass + write pass with padding
     const bool onepass = c->sw.emit_onepass && cache == 0 && slot_cap >= 9 * n;
     if (n) c->path_k3 = std::max<u32>(c->path_k3, onepass ? RDF_TEST_K3_ONEPASS : RDF_TEST_K3_TWOPASS);
+    // ... and the emission blocks count the record sort's first digit themselves (k_emit_records<.., HIST>): the sort's
+    // first pass scatters the regions straight into rec (radix_seg_first_pass), so the regions are not compacted, the
+    // block counts not scanned and the records not read a third time by a count pass.  The first pass is queued before
+    // the one read-back (kept, emitted and the scatter's overflow word: it needs no count from the host, its writes are
+    // bounded by the buffer).  RDFIND_EMIT_HIST=0: the compaction form below
+    // (the scatter is bounded by the buffers' capacity, which it takes for a key count below 2^32: every caller's one-pass
+    // buffers hold 9n < 2^32 slots, larger inputs build their groups in join ranges)
+    if (onepass && n && c->sw.emit_hist && capbits + joinbits > 0 && slot_cap < (1ull << 32)) {
+        const int bits = capbits + joinbits, w0 = radix_first_width(bits);
+        u64* eb = c->eblk.as<u64>();
+        u32* over32 = (u32*)dscal(c, 9);  // (zeroed above)
+        HIP_TRY(c, hipMemsetAsync(eb + eg, 0, 16, st));  // records emitted (repeats included), records kept
+        u32* hist = radix_seg_hist(c->ws, eg, w0);
+        if (!hist) return fail(c, RDF_ERR_OOM, "K3: the first sort digit's histogram");
+        const u32 hs = radix_seg_stride(eg);
+        if (lazy)
+            hipLaunchKernelGGL((k_emit_records<true, true, true>), dim3(eg), dim3(RDF_BLOCK), 0, st, c->s, c->p, c->o, n, per, V,
+                               2u * c->U, c->frank.as<u32>(), c->lkeys.as<u64>(), c->lvals.as<u32>(), c->lcap - 1, proj,
+                               joinbits, js, eb, (const u64*)nullptr, c->rec_tmp.as<u64>(), bits, hist, hs, w0);
+        else
+            hipLaunchKernelGGL((k_emit_records<true, false, true>), dim3(eg), dim3(RDF_BLOCK), 0, st, c->s, c->p, c->o, n, per, V,
+                               2u * c->U, c->frank.as<u32>(), c->lkeys.as<u64>(), c->lvals.as<u32>(), c->lcap - 1, proj,
+                               joinbits, js, eb, (const u64*)nullptr, c->rec_tmp.as<u64>(), bits, hist, hs, w0);
+        HIP_TRY(c, hipGetLastError());
+        tend(c, RDF_T_EMIT);
+        tbegin(c, RDF_T_SORT);
+        HIP_TRY(c, radix_seg_first_pass(c->ws, c->rec_tmp.as<u64>(), slot_cap, ebuf, slot_cap, nullptr, 9 * per, eb, eg, w0, hist,
+                                        over32, st));
+        u64 v[3];
+        TRY(read_multi(c, {{eb + eg + 1, 8}, {eb + eg, 8}, {over32, 4}}, v));
+        if (v[2])
+            return fail(c, RDF_ERR_LIMIT, "K3: the emission's digit histogram and its records disagree (the sort's first "
+                                          "pass wrote nothing past its buffer)");
+        const u64 Je = v[0];  // the kept records, all of them sorted; the emitted ones count as n_records
+        if (Je > slot_cap) return fail(c, RDF_ERR_LIMIT, "K3 emitted more records than the join range was sized for");
+        c->J_emit += std::max(v[1], Je);
+        c->k3_hist = true;
+        u64 *keys = ebuf, *tmp = c->rec_tmp.as<u64>();
+        HIP_TRY(c, radix_sort_u64_rest(c->ws, keys, tmp, Je, w0, bits, st));
+        tend(c, RDF_T_SORT);
+        c->sort_passes_records += (u64)radix_sort_passes(bits) * Je;
+        return g_support_sorted(c, keys, Je, sup, Jout);
+    }
     if (onepass && n) {
         u64* eoff = c->eblk.as<u64>() + (eg + 1ull);
         HIP_TRY(c, hipMemsetAsync(c->eblk.as<u64>() + eg, 0, 8, st));  // records emitted, repeats included
@@ -2219,7 +2268,6 @@ static rdf_status g_fresh_bounds(rdf_ctx* c, const u64* keys, u64 J) {
 // passes).  Sets c->rec_sorted, *Jout.
 static rdf_status g_sort_support(rdf_ctx* c, u64* keys, u64* tmp, u64 Je, u32* sup, u64* Jout, u64* keep_out) {
     hipStream_t st = c->stream;
-    const u64 ncap = c->ncap;
     const int capbits = c->capbits, joinbits = c->joinbits;
     c->J_emit += Je;
     u64 J = 0;
@@ -2230,9 +2278,16 @@ static rdf_status g_sort_support(rdf_ctx* c, u64* keys, u64* tmp, u64 Je, u32* s
         keys = keep_out;
     }
     tend(c, RDF_T_SORT);
+    c->sort_passes_records += Je + (u64)(radix_sort_passes(capbits + joinbits) - 1) * J;
+    return g_support_sorted(c, keys, J, sup, Jout);
+}
+
+// K5 supports of J sorted records -> sup.  Sets c->rec_sorted, *Jout.
+static rdf_status g_support_sorted(rdf_ctx* c, u64* keys, u64 J, u32* sup, u64* Jout) {
+    hipStream_t st = c->stream;
+    const u64 ncap = c->ncap;
     *Jout = J;
     c->rec_sorted = keys;
-    c->sort_passes_records += Je + (u64)(radix_sort_passes(capbits + joinbits) - 1) * J;
     // supports = distinct join values per capture: fresh (capture, join) records counted per key run
     ENSURE(c, flags, std::max<u64>(J, 1) * 4);
     ENSURE(c, fpos, (J + 1) * 4);

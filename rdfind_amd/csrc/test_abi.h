@@ -57,6 +57,18 @@ rdf_status rdf_test_radix(rdf_ctx* ctx, int op, const void* keys_host, uint64_t 
 /* radix_sort_passes(bits) */
 int rdf_test_radix_passes(int bits);
 
+/* The sort of keys that lie in segments (radix_seg_first_pass + radix_sort_u64_rest): segment b is seg_cnt[b] keys of
+ * src_host[0, src_n) from seg_base[b] on (seg_base null: from b * stride on); the keys between the segments are not
+ * part of the sort.  The call builds the segments' histogram of the low w0 bits on the host (w0 = 0: the width
+ * radix_first_width(bits) gives), adds hist_bump to the count of digit hist_bump_digit of segment hist_bump_seg (0: the
+ * true histogram; otherwise the primitive must report the disagreement: RDF_ERR_LIMIT), runs the first pass over the
+ * segments and the remaining passes on bits [w0, bits).  out_host holds the segments' keys (sum of seg_cnt); *n_out =
+ * their number.  Segments that overlap or leave src_host are refused (RDF_ERR_ARG). */
+rdf_status rdf_test_radix_segments(rdf_ctx* ctx, const uint64_t* src_host, uint64_t src_n, const uint64_t* seg_base,
+                                   uint64_t stride, const uint64_t* seg_cnt, uint32_t n_seg, int w0, int bits,
+                                   int32_t hist_bump, uint32_t hist_bump_seg, uint32_t hist_bump_digit,
+                                   uint64_t* out_host, uint64_t* n_out, uint32_t* canaries_ok);
+
 /* Paths of the last completed run (RDF_ERR_STATE without one).  0 in a form field: that stage made no choice
  * (K2 and K3 of an input without triples). */
 enum { RDF_TEST_K1_PARTITIONED = 1, RDF_TEST_K1_RADIX = 2, RDF_TEST_K1_ATOMIC = 3 };
@@ -85,6 +97,7 @@ typedef struct rdf_test_path_report {
     uint32_t light_two_pass;       /* the two light passes */
     uint32_t sig_on;               /* the run computed light-group signatures */
     uint32_t piv2_on;              /* ... and second pivots */
+    uint32_t k3_hist;              /* K3 counted the record sort's first digit: the sort's first pass read K3's regions */
 } rdf_test_path_report;
 
 rdf_status rdf_test_paths(rdf_ctx* ctx, rdf_test_path_report* out);

@@ -178,6 +178,71 @@ rdf_status rdf_test_radix(rdf_ctx* c, int op, const void* keys_host, uint64_t n,
 
 int rdf_test_radix_passes(int bits) { return radix_sort_passes(bits); }
 
+rdf_status rdf_test_radix_segments(rdf_ctx* c, const uint64_t* src_host, uint64_t src_n, const uint64_t* seg_base,
+                                   uint64_t stride, const uint64_t* seg_cnt, uint32_t n_seg, int w0, int bits,
+                                   int32_t hist_bump, uint32_t hist_bump_seg, uint32_t hist_bump_digit,
+                                   uint64_t* out_host, uint64_t* n_out, uint32_t* canaries_ok) {
+    if (!c) return RDF_ERR_ARG;
+    if (!canaries_ok || !n_out || !seg_cnt || (src_n && !src_host))
+        return fail(c, RDF_ERR_ARG, "rdf_test_radix_segments: null argument");
+    *canaries_ok = 0;
+    *n_out = 0;
+    if (w0 == 0) w0 = radix_first_width(bits);
+    if (n_seg == 0 || n_seg > (1u << 16) || bits < 1 || bits > 64 || w0 < 1 || w0 > RS_MAX_BITS || w0 > bits ||
+        src_n >= (1ull << 32))
+        return fail(c, RDF_ERR_ARG, "rdf_test_radix_segments: segments, bits or width out of range");
+    if (!seg_layout_ok(src_n, seg_base, stride, seg_cnt, n_seg))
+        return fail(c, RDF_ERR_ARG, "rdf_test_radix_segments: a segment leaves the keys or overlaps another");
+    std::vector<u32> hh;
+    const u64 total = seg_host_histogram(src_host, seg_base, stride, seg_cnt, n_seg, w0, hh);
+    if (total && !out_host) return fail(c, RDF_ERR_ARG, "rdf_test_radix_segments: null argument");
+    if (hist_bump) {
+        if (hist_bump_seg >= n_seg || hist_bump_digit >= (1u << w0))
+            return fail(c, RDF_ERR_ARG, "rdf_test_radix_segments: the changed histogram entry is out of range");
+        hh[(size_t)hist_bump_digit * radix_hist_stride(n_seg) + hist_bump_seg] += (u32)hist_bump;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    TestArr src, a, b, cnt, base, over;  // the first pass reads src and writes a; the later passes write b and a in turn
+    HIP_TRY(c, src.make(8, src_n, 0, st));
+    HIP_TRY(c, a.make(8, total, 0, st));
+    HIP_TRY(c, b.make(8, total, 0, st));
+    HIP_TRY(c, cnt.make(8, n_seg, 0, st));
+    HIP_TRY(c, base.make(8, n_seg, 0, st));
+    HIP_TRY(c, over.make(4, 1, 0, st));
+    if (src_n) HIP_TRY(c, hipMemcpyAsync(src.data(), src_host, src_n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(cnt.data(), seg_cnt, n_seg * 8ull, hipMemcpyHostToDevice, st));
+    if (seg_base) HIP_TRY(c, hipMemcpyAsync(base.data(), seg_base, n_seg * 8ull, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(over.data(), 0, 4, st));
+    u64 *keys = (u64*)a.data(), *tmp = (u64*)b.data();
+    hipError_t e = hipSuccess;
+    u32* hist = radix_seg_hist(c->ws, n_seg, w0);
+    if (!hist) e = hipErrorOutOfMemory;
+    if (e == hipSuccess) e = hipMemcpyAsync(hist, hh.data(), hh.size() * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = radix_seg_first_pass(c->ws, (const u64*)src.data(), src_n, keys, total, seg_base ? (const u64*)base.data() : nullptr,
+                                 stride, (const u64*)cnt.data(), n_seg, w0, hist, (u32*)over.data(), st);
+    u32 h_over = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&h_over, over.data(), 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && !h_over) e = radix_sort_u64_rest(c->ws, keys, tmp, total, w0, bits, st);
+    HIP_TRY(c, hipStreamSynchronize(st));
+    bool ok = true;
+    HIP_TRY(c, check_canaries(src, &ok));
+    HIP_TRY(c, check_contents(src, src_host, src_n, &ok));  // the segments are read only
+    HIP_TRY(c, check_canaries(a, &ok));
+    HIP_TRY(c, check_canaries(b, &ok));
+    HIP_TRY(c, check_canaries(cnt, &ok));
+    HIP_TRY(c, check_canaries(base, &ok));
+    HIP_TRY(c, check_canaries(over, &ok));
+    *canaries_ok = ok ? 1 : 0;
+    TRY(prim_status(c, e, "radix segment sort"));
+    if (h_over) return fail(c, RDF_ERR_LIMIT, "rdf_test_radix_segments: the histogram and the segments' keys disagree");
+    if (total) HIP_TRY(c, hipMemcpy(out_host, keys, total * 8, hipMemcpyDeviceToHost));
+    *n_out = total;
+    return RDF_OK;
+}
+
 rdf_status rdf_test_paths(rdf_ctx* c, rdf_test_path_report* out) {
     if (!c || !out) return RDF_ERR_ARG;
     if (c->stage < 4) return fail(c, RDF_ERR_STATE, "no completed run");
@@ -203,6 +268,7 @@ rdf_status rdf_test_paths(rdf_ctx* c, rdf_test_path_report* out) {
     r.light_two_pass = c->lpaths.two_pass ? 1 : 0;
     r.sig_on = c->sig_on ? 1 : 0;
     r.piv2_on = c->piv2_on ? 1 : 0;
+    r.k3_hist = c->k3_hist ? 1 : 0;
     *out = r;
     return RDF_OK;
 }
