@@ -47,7 +47,8 @@ RDF_NT_TABS = 1
 
 # the test-only entry points of rdfind_amd/csrc/test_abi.h (not part of the product ABI)
 TEST_SYMBOLS = ("rdf_test_scan", "rdf_test_scan_batch", "rdf_test_radix", "rdf_test_radix_passes",
-                "rdf_test_radix_segments", "rdf_test_paths", "rdf_test_rewrite_form", "rdf_test_cind_stats_times")
+                "rdf_test_radix_segments", "rdf_test_paths", "rdf_test_rewrite_form", "rdf_test_cind_stats_times",
+                "rdf_test_fc_trace", "rdf_test_fc_report", "rdf_test_copy_frequent_unary", "rdf_test_unary_lookup")
 REWRITE_FORMS = {0: None, 1: "lds", 2: "global"}
 SCAN_U32_U32, SCAN_U32_U64, SCAN_U64_U64 = range(3)
 SCAN_DTYPES = {SCAN_U32_U32: (np.uint32, np.uint32), SCAN_U32_U64: (np.uint32, np.uint64),
@@ -114,6 +115,14 @@ class PathReport(ctypes.Structure):
                 ("light_npx", ctypes.c_uint32), ("packed_npx", ctypes.c_uint32), ("light_ordered", ctypes.c_uint32),
                 ("light_side", ctypes.c_uint32), ("light_two_pass", ctypes.c_uint32), ("sig_on", ctypes.c_uint32),
                 ("piv2_on", ctypes.c_uint32), ("k3_hist", ctypes.c_uint32)]
+
+
+class FcReport(ctypes.Structure):
+    """rdf_test_fc_report_t (rdfind_amd/csrc/test_abi.h)."""
+    _fields_ = [("traced", ctypes.c_uint32), ("k1_form", ctypes.c_uint32), ("k1_bits", ctypes.c_uint32),
+                ("k2_form", ctypes.c_uint32), ("k2_bits", ctypes.c_uint32), ("k2_sub", ctypes.c_uint32),
+                ("k1_buckets", ctypes.c_uint64), ("k1_slices", ctypes.c_uint64), ("k1_multi", ctypes.c_uint64),
+                ("k2_buckets", ctypes.c_uint64), ("k2_multi", ctypes.c_uint64), ("k2_spill", ctypes.c_uint64)]
 
 
 class ResultLayout(ctypes.Structure):
@@ -267,6 +276,10 @@ def load():
         "rdf_test_paths": (i32, [P, ctypes.POINTER(PathReport)]),
         "rdf_test_rewrite_form": (i32, [P, ctypes.POINTER(u32)]),
         "rdf_test_cind_stats_times": (i32, [P, ctypes.POINTER(ctypes.c_float)]),
+        "rdf_test_fc_trace": (i32, [P, ctypes.c_int]),
+        "rdf_test_fc_report": (i32, [P, ctypes.POINTER(FcReport)]),
+        "rdf_test_copy_frequent_unary": (i32, [P, P, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "rdf_test_unary_lookup": (i32, [P, P, u64, P, P, ctypes.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None) if name in TEST_SYMBOLS else getattr(lib, name)
@@ -728,6 +741,41 @@ class Context:
                      "piv2_on", "k3_hist"):
             d[name] = bool(d[name])
         return d
+
+    def test_fc_trace(self, on: bool = True):
+        """rdf_test_fc_trace: while on, frequent_conditions reads its slice lists back for :meth:`test_fc_report`."""
+        self._check(self._test_fn("rdf_test_fc_trace")(self.ptr, int(on)), "rdf_test_fc_trace")
+
+    def test_fc_report(self) -> dict:
+        """The shape of the last frequent_conditions (rdf_test_fc_report): the K1 / K2 forms by name, k1_bits,
+        k1_buckets, k2_bits, k2_sub, k2_buckets, k2_spill, and (``traced``: the stage ran under :meth:`test_fc_trace`)
+        k1_slices, k1_multi, k2_multi."""
+        r = FcReport()
+        self._check(self._test_fn("rdf_test_fc_report")(self.ptr, ctypes.byref(r)), "rdf_test_fc_report")
+        d = _struct_dict(r)
+        d["k1_form"], d["k2_form"], d["traced"] = K1_FORMS[r.k1_form], K2_FORMS[r.k2_form], bool(r.traced)
+        return d
+
+    def test_copy_frequent_unary(self):
+        """(fval[0, U), [frequent s, p, o]) of the last frequent_conditions (rdf_test_copy_frequent_unary)."""
+        U, n3 = ctypes.c_uint64(), (ctypes.c_uint64 * 3)()
+        fn = self._test_fn("rdf_test_copy_frequent_unary")
+        if fn(self.ptr, None, 0, ctypes.byref(U), n3) != 0 and U.value == 0:  # (cap 0 < U fails after it told U)
+            self._check(-1, "rdf_test_copy_frequent_unary")
+        out = np.empty(U.value, np.uint32)
+        self._check(fn(self.ptr, out.ctypes.data, out.shape[0], ctypes.byref(U), n3), "rdf_test_copy_frequent_unary")
+        return out[: U.value], [int(x) for x in n3]
+
+    def test_unary_lookup(self, keys):
+        """(rank, bit, canaries_ok) of the unary keys ``pos * V + value`` (rdf_test_unary_lookup): the global rank among
+        the frequent conditions (0xffffffff: none) and the key's bit of the frequency bitmap."""
+        k = np.ascontiguousarray(keys, dtype=np.uint64)
+        rank, bit, ok = np.empty(k.shape[0], np.uint32), np.empty(k.shape[0], np.uint32), ctypes.c_uint32()
+        rc = self._test_fn("rdf_test_unary_lookup")(self.ptr, k.ctypes.data, k.shape[0], rank.ctypes.data, bit.ctypes.data,
+                                                    ctypes.byref(ok))
+        self.test_canaries_ok = bool(ok.value)
+        self._check(rc, "rdf_test_unary_lookup")
+        return rank, bit, bool(ok.value)
 
     # -- sharded mode (driven by rdfind_amd.distributed.run_sharded) ---------------------------
     def shard_begin(self, rank: int, nranks: int, min_support: int, projection="spo", clean_implied=True,

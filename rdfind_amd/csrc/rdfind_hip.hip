@@ -270,6 +270,10 @@ struct rdf_ctx : CtxBuffers {
     u64 n_dense_eligible = 0;             // groups d_dense_flags numbered (n_dense: the rows d_dense_build gave a bitmap)
     // which alternative ran at the run's decision points (RDF_TEST_K1_* / K2_* / K3_*, test_abi.h; 0: none yet)
     u32 path_k1 = 0, path_k2 = 0, path_k3 = 0;
+    // rdf_test_fc_trace / rdf_test_fc_report (test_abi.h): the shape of the last frequent-condition stage; with fc_trace
+    // on, the stage also reads its slice lists back (fc_trace_slices)
+    bool fc_trace = false;
+    rdf_test_fc_report_t fcrep = {};
     // the last group build's K3 handed the record sort its first digit histogram (RDFIND_EMIT_HIST)
     bool k3_hist = false;
     // what the light launches of the last discovery were given (d_light_kernels; sums over its pages, ranges and
@@ -1455,6 +1459,17 @@ rdf_status rdf_rewrite_terms(rdf_ctx* c, uint32_t flags, const char* key_heap, c
 // ------------------------------------------------------------------------------------------------
 // Stage 1: frequent conditions (FrequentConditionPlanner.constructFrequentConditionPlan)
 
+// rdf_test_fc_trace: the scanned slice list soff[0, NB] of a counting stage read back; *slices = its slices (a bucket
+// without records has one too), *multi = the buckets with more than one
+static rdf_status fc_trace_slices(rdf_ctx* c, const u32* soff, u64 NB, uint64_t* slices, uint64_t* multi) {
+    std::vector<u32> h(NB + 1);
+    HIP_TRY(c, ctx_copy(c, h.data(), soff, (NB + 1) * 4, hipMemcpyDeviceToHost));
+    *slices = h[NB];
+    *multi = 0;
+    for (u64 b = 0; b < NB; ++b) *multi += h[b + 1] - h[b] > 1;
+    return RDF_OK;
+}
+
 // K1 partitioned over (s, p, o, n): bucket histogram, scatter of the low key bits, per-bucket LDS counting.
 // counts_only: the dense counts land in cntg (sharded input: their nonzero entries go to the keys' owners);
 // otherwise ranks, fbits and the rank-block totals bfreq are written (fc_unary_finish makes them global).
@@ -1503,6 +1518,9 @@ static rdf_status fc_unary_part(rdf_ctx* c, const u32* s, const u32* p, const u3
     hipLaunchKernelGGL(k_u2_slices, dim3((unsigned)NB), dim3(RDF_BLOCK), 0, st, c->uhist.as<u32>(), (u32)NB, G, ubits, K,
                        c->usl.as<u32>(), c->cntg.as<u32>());
     HIP_TRY(c, exclusive_scan_u32(c->ws, c->usl.as<u32>(), c->usl.as<u32>(), NB, c->usl.as<u32>() + NB, st));
+    c->fcrep.k1_bits = (u32)ubits;
+    c->fcrep.k1_buckets = NB;
+    if (c->fc_trace) TRY(fc_trace_slices(c, c->usl.as<u32>(), NB, &c->fcrep.k1_slices, &c->fcrep.k1_multi));
     const u64 max_slices = NB + 3 * n / U2_SLICE + 1;  // >= sum over buckets of max(1, ceil(len / U2_SLICE))
     const int co = counts_only ? 1 : 0;
 #define RDF_U2_COUNT(BITS, RT)                                                                                           \
@@ -1694,6 +1712,7 @@ static rdf_status fc_binary_part(rdf_ctx* c, const u32* s, const u32* p, const u
         hipLaunchKernelGGL(k_b2_hbounds, dim3(grid_for(R + 1, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, keys, R, T,
                            c->bstart2.as<u32>());
         HIP_TRY(c, hipGetLastError());
+        c->fcrep.k2_bits = (u32)T;
         return fc_binary_count(c, keys, c->bstart2.as<u32>(), NBh, 1, partials, B, nkeys, S);
     }
     const size_t lds = (size_t)NB2 * 4;
@@ -1720,6 +1739,8 @@ static rdf_status fc_binary_part(rdf_ctx* c, const u32* s, const u32* p, const u
     const u32* bstart = c->uhist.as<u32>();
     u32 NBc = NB2, Gc = G2;
     c->path_k2 = sub ? RDF_TEST_K2_SPLIT : RDF_TEST_K2_PLAIN;
+    c->fcrep.k2_bits = (u32)bits;
+    c->fcrep.k2_sub = (u32)sub;
     if (sub) {
         NBc = NB2 << sub;
         Gc = 1;
@@ -1748,6 +1769,11 @@ static rdf_status fc_binary_count(rdf_ctx* c, const u64* recs, const u32* bstart
     hipLaunchKernelGGL(k_b2_slices, dim3(grid_for(NBc, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, bstart, NBc, Gc,
                        c->usl.as<u32>());
     HIP_TRY(c, exclusive_scan_u32(c->ws, c->usl.as<u32>(), c->usl.as<u32>(), NBc, c->usl.as<u32>() + NBc, st));
+    c->fcrep.k2_buckets = NBc;
+    if (c->fc_trace) {
+        uint64_t slices = 0;
+        TRY(fc_trace_slices(c, c->usl.as<u32>(), NBc, &slices, &c->fcrep.k2_multi));
+    }
     HIP_TRY(c, hipMemsetAsync(dscal(c, 3), 0, 3 * 8, st));
     hipLaunchKernelGGL(k_b2_count, dim3(256 * 3), dim3(RDF_BLOCK), 0, st, recs, bstart, c->usl.as<u32>(), NBc, Gc, c->ms, c->bkeys.as<u64>(), c->tkeys.as<u64>(),
                        (u32*)c->pos.p, dscal(c, 3), partials ? 1 : 0);
@@ -1755,6 +1781,7 @@ static rdf_status fc_binary_count(rdf_ctx* c, const u64* recs, const u32* bstart
     *B = c->hscal[3];
     *nkeys = c->hscal[4];
     *S = c->hscal[5];
+    c->fcrep.k2_spill = *S;
     if (!partials && *S) TRY(fc_sum_pairs(c, c->tkeys.as<u64>(), (const u32*)c->pos.p, *S, B, nkeys));
     return RDF_OK;
 }
@@ -1857,6 +1884,8 @@ static rdf_status fc_begin(rdf_ctx* c, uint32_t min_support) {
     c->class_pending = false;
     c->paged = c->cs_open = c->cs_top_valid = false;
     c->path_k1 = c->path_k2 = 0;
+    c->fcrep = {};
+    c->fcrep.traced = c->fc_trace ? 1 : 0;
     for (int i = 0; i < RDF_NUM_TIMERS; ++i) c->tn[i] = 0;  // a failed run may have left segments behind
     c->pend_fc = c->pend_groups = c->pend_heavy = false;
     c->spare_fc = false;  // this stage's scratch is in use again

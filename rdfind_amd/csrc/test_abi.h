@@ -1,10 +1,11 @@
 /* Test-only entry points of librdfind_hip.so (rdf_test_*): the scan and radix primitives of primitives.hip on
- * caller-given data, a report of the paths the last run took, and the split timing of the result statistics.  Not part of
- * the product ABI
- * (include/rdfind_hip.h): bound by rdfind_amd/_lib.py for tests/test_gpu_primitives.py and the forced-path tests.
+ * caller-given data, a report of the paths the last run took, the frequent-condition stage's shape and unary set, and
+ * the split timing of the result statistics.  Not part of the product ABI (include/rdfind_hip.h): bound by
+ * rdfind_amd/_lib.py for tests/test_gpu_primitives.py, tests/test_gpu_fc.py and the forced-path tests.
  *
  * Every call runs on the context's stream with the context's workspace, touches no pipeline state (the stage and
- * the last result stay) and fails with an rdf_status and rdf_last_error like the product calls.
+ * the last result stay; rdf_test_fc_trace sets a flag the next rdf_frequent_conditions reads) and fails with an
+ * rdf_status and rdf_last_error like the product calls.
  *
  * Canaries: each call allocates its device buffers itself, with RDF_TEST_CANARY elements of the byte pattern
  * RDF_TEST_CANARY_BYTE directly before and directly after every range a primitive may write.  *canaries_ok = 1 when
@@ -101,6 +102,42 @@ typedef struct rdf_test_path_report {
 } rdf_test_path_report;
 
 rdf_status rdf_test_paths(rdf_ctx* ctx, rdf_test_path_report* out);
+
+/* Frequent-condition counting (K1 / K2, counts.inl) on its own: which branches the last rdf_frequent_conditions took,
+ * and the frequent unary set it left on the device.  All four calls need only that stage (RDF_ERR_STATE before it and
+ * after rdf_release_scratch), not a whole run.
+ *
+ * rdf_test_fc_trace: off by default.  Only while it is on does rdf_frequent_conditions read the K1 and K2 slice lists
+ * back (two copies and host waits more) to fill the slice fields of the report; off, the stage issues the launches and
+ * host waits it always did, and those fields are zero. */
+rdf_status rdf_test_fc_trace(rdf_ctx* ctx, int on);
+
+typedef struct rdf_test_fc_report_t {
+    uint32_t traced;      /* the stage ran with the trace on: the fields marked (t) are filled */
+    uint32_t k1_form;     /* RDF_TEST_K1_* */
+    uint32_t k1_bits;     /* key bits per K1 bucket: 14 or 15 (0: the atomic form has no buckets) */
+    uint32_t k2_form;     /* RDF_TEST_K2_* (0: no triples) */
+    uint32_t k2_bits;     /* bucket bits of K2's first level (the radix form: of its hash prefix) */
+    uint32_t k2_sub;      /* bits of the second-level split (k_b2_split), 0 without one */
+    uint64_t k1_buckets;  /* K1 buckets */
+    uint64_t k1_slices;   /* (t) K1 counting slices (a bucket without records has one too) */
+    uint64_t k1_multi;    /* (t) K1 buckets counted by more than one slice (ranked by k_u2_finish) */
+    uint64_t k2_buckets;  /* K2 counting buckets (first level << sub) */
+    uint64_t k2_multi;    /* (t) K2 buckets counted by more than one slice (all partials to the spill list) */
+    uint64_t k2_spill;    /* spill entries handed to fc_sum_pairs: partials of multi-slice buckets + refused records */
+} rdf_test_fc_report_t;
+
+rdf_status rdf_test_fc_report(rdf_ctx* ctx, rdf_test_fc_report_t* out);
+
+/* fval[0, U) (the values of the frequent unary conditions in rank order: subjects, predicates, objects, each ascending)
+ * into fval_host[0, cap), *U_out = U, n3 = the frequent s / p / o counts.  cap < U: RDF_ERR_ARG, nothing copied. */
+rdf_status rdf_test_copy_frequent_unary(rdf_ctx* ctx, uint32_t* fval_host, uint64_t cap, uint64_t* U_out, uint64_t* n3);
+
+/* rank_out[i] = the global rank of unary key keys[i] = pos * V + value among the frequent conditions (0xffffffff: not
+ * frequent), bit_out[i] = its bit of the frequency bitmap K2 reads.  A gather on the device: nothing sized by |V| moves.
+ * A key >= 3V is refused (RDF_ERR_ARG) before anything runs; the outputs lie between canaries. */
+rdf_status rdf_test_unary_lookup(rdf_ctx* ctx, const uint64_t* keys, uint64_t n, uint32_t* rank_out, uint32_t* bit_out,
+                                 uint32_t* canaries_ok);
 
 /* The key lookup of the last rdf_rewrite_terms: the tables staged in LDS, or read from global memory (a table too
  * large for LDS).  0: no call yet, or the last one had no keys or no terms. */

@@ -51,6 +51,23 @@ static rdf_status prim_status(rdf_ctx* c, hipError_t e, const char* what) {
     return fail(c, e == hipErrorOutOfMemory ? RDF_ERR_OOM : RDF_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// rdf_test_unary_lookup: rank[i] = frank[keys[i]] (global ranks after the stage), bit[i] = the key's fbits bit
+__global__ __launch_bounds__(RDF_BLOCK) void k_test_unary_lookup(const u64* __restrict__ keys, u64 n,
+                                                                 const u32* __restrict__ frank,
+                                                                 const u64* __restrict__ fbits, u32* rank, u32* bit) {
+    for (u64 i = (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * RDF_BLOCK) {
+        rank[i] = frank[keys[i]];
+        bit[i] = fbit(fbits, keys[i]) ? 1u : 0u;
+    }
+}
+
+// the frequent-condition state these calls read: the stage is done, single GPU, and its buffers are still held
+static rdf_status fc_state(rdf_ctx* c, const char* who) {
+    if (c->stage < 2 || c->nranks != 1 || !c->frank.p || !c->fbits.p || !c->fval.p)
+        return fail(c, RDF_ERR_STATE, std::string(who) + ": rdf_frequent_conditions must be called first");
+    return RDF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -270,6 +287,71 @@ rdf_status rdf_test_paths(rdf_ctx* c, rdf_test_path_report* out) {
     r.piv2_on = c->piv2_on ? 1 : 0;
     r.k3_hist = c->k3_hist ? 1 : 0;
     *out = r;
+    return RDF_OK;
+}
+
+rdf_status rdf_test_fc_trace(rdf_ctx* c, int on) {
+    if (!c) return RDF_ERR_ARG;
+    c->fc_trace = on != 0;
+    return RDF_OK;
+}
+
+rdf_status rdf_test_fc_report(rdf_ctx* c, rdf_test_fc_report_t* out) {
+    if (!c || !out) return RDF_ERR_ARG;
+    if (c->stage < 2) return fail(c, RDF_ERR_STATE, "rdf_test_fc_report: rdf_frequent_conditions must be called first");
+    *out = c->fcrep;
+    out->k1_form = c->path_k1;
+    out->k2_form = c->path_k2;
+    return RDF_OK;
+}
+
+rdf_status rdf_test_copy_frequent_unary(rdf_ctx* c, uint32_t* fval_host, uint64_t cap, uint64_t* U_out, uint64_t* n3) {
+    if (!c) return RDF_ERR_ARG;
+    if (!U_out || !n3 || (cap && !fval_host)) return fail(c, RDF_ERR_ARG, "rdf_test_copy_frequent_unary: null argument");
+    TRY(fc_state(c, "rdf_test_copy_frequent_unary"));
+    *U_out = c->U;
+    for (int t = 0; t < 3; ++t) n3[t] = c->fstats.n_frequent_unary[t];
+    if (cap < c->U) return fail(c, RDF_ERR_ARG, "rdf_test_copy_frequent_unary: fval_host holds fewer than U values");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->U) HIP_TRY(c, ctx_copy(c, fval_host, c->fval.p, (size_t)c->U * 4, hipMemcpyDeviceToHost));
+    return RDF_OK;
+}
+
+rdf_status rdf_test_unary_lookup(rdf_ctx* c, const uint64_t* keys, uint64_t n, uint32_t* rank_out, uint32_t* bit_out,
+                                 uint32_t* canaries_ok) {
+    if (!c) return RDF_ERR_ARG;
+    if (!canaries_ok || (n && (!keys || !rank_out || !bit_out)))
+        return fail(c, RDF_ERR_ARG, "rdf_test_unary_lookup: null argument");
+    *canaries_ok = 0;
+    TRY(fc_state(c, "rdf_test_unary_lookup"));
+    const u64 K = 3ull * (c->V ? c->V : 1);
+    for (u64 i = 0; i < n; ++i)
+        if (keys[i] >= K) return fail(c, RDF_ERR_ARG, "rdf_test_unary_lookup: a key is not below 3V");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    TestArr dk, dr, db;
+    HIP_TRY(c, dk.make(8, n, 0, st));
+    HIP_TRY(c, dr.make(4, n, 0, st));
+    HIP_TRY(c, db.make(4, n, 0, st));
+    if (n) {
+        HIP_TRY(c, hipMemcpyAsync(dk.data(), keys, n * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_test_unary_lookup, dim3(grid_for(n, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st,
+                           (const u64*)dk.data(), n, c->frank.as<u32>(), c->fbits.as<u64>(), (u32*)dr.data(),
+                           (u32*)db.data());
+    }
+    const hipError_t e = n ? hipGetLastError() : hipSuccess;
+    HIP_TRY(c, hipStreamSynchronize(st));
+    bool ok = true;
+    HIP_TRY(c, check_canaries(dk, &ok));
+    HIP_TRY(c, check_contents(dk, keys, n, &ok));  // the keys are read only
+    HIP_TRY(c, check_canaries(dr, &ok));
+    HIP_TRY(c, check_canaries(db, &ok));
+    *canaries_ok = ok ? 1 : 0;
+    TRY(prim_status(c, e, "k_test_unary_lookup"));
+    if (n) {
+        HIP_TRY(c, hipMemcpy(rank_out, dr.data(), n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(bit_out, db.data(), n * 4, hipMemcpyDeviceToHost));
+    }
     return RDF_OK;
 }
 

@@ -169,6 +169,7 @@ def test_synthetic_configs_vs_oracle(ctx, cfg, scale):
     st = assert_rows_equal(ctx, d, 1, True)
     assert ctx.fc["n_frequent_unary"] == st["n_freq_unary"]
     assert ctx.fc["n_frequent_binary"] == st["n_freq_binary"]
+    assert ctx.fc["n_binary_keys"] == st["n_binary_keys"]
     assert ctx.groups["n_records"] == st["n_records"]
     assert ctx.groups["n_captures"] == st["n_freq_captures"]
     assert_stream_matches(ctx, cfg, scale)
