@@ -545,6 +545,68 @@ typedef struct {
 } rdf_top_ref;
 rdf_status rdf_copy_top_refs(rdf_ctx* ctx, rdf_top_ref* out, uint64_t cap, uint64_t* n_copied);
 
+/*
+ * Result selection on the device: the CINDs of the current result whose dependent, referenced capture and support
+ * match a query, read from the result as it lies in HBM.  A pending class part (members x shared lists) is selected in
+ * O(members + list refs + selected rows) per class and stays pending; nothing is expanded.
+ *
+ * A capture matches a pattern when its code is admitted by `codes` and its condition values equal value1 / value2
+ * wherever those are not RDF_SEL_ANY.  A CIND (dep, ref, support) is selected when dep matches any of the query's dep
+ * patterns (or n_dep == 0), ref matches any of its ref patterns (or n_ref == 0) and min_support <= support <=
+ * max_support, the support being the dependent's.  The empty query selects every row.
+ *
+ *   rdf_select_cinds         selects from the current result: the whole result after rdf_discover_cinds / rdf_run, the
+ *                            current page after rdf_next_page.  Leaves a selection view in HBM in the result's own form
+ *                            (refs in runs of one dependent, compact capture ids, runs without a selected ref dropped;
+ *                            runs in the order of the result, the explicit ones before the class members', refs in
+ *                            source order within a run); *n_selected receives its row count, *ms (optional) the device
+ *                            time.  With RDF_SEL_COUNT_ONLY it stops after counting: no view is written and an earlier
+ *                            one is dropped.  Errors: RDF_ERR_LIMIT for more than RDF_SEL_MAX_PATTERNS patterns on a
+ *                            side; RDF_ERR_ARG for codes outside 0x1ff, min_support > max_support, unknown flags or a
+ *                            null pattern array with a count; RDF_ERR_STATE without a current result or after a sharded
+ *                            run (a rank holds its own dependents only); RDF_ERR_OOM when the view does not fit
+ *                            (rdf_last_error names the bytes it needs), which leaves no view.
+ *   rdf_selected_count       rows of the view.
+ *   rdf_copy_selected_decoded, rdf_format_selected_size, rdf_format_selected
+ *                            rdf_copy_cinds_decoded / rdf_format_size / rdf_format_cinds on the view's rows [offset,
+ *                            offset + count) (clipped against the view, rows in view order); the formatting calls need
+ *                            rdf_set_dictionary as theirs do, and a cap that is too small returns RDF_ERR_ARG with
+ *                            *bytes set.
+ * The view lives until the next rdf_select_cinds, rdf_next_page, a new discovery (paged or not), new triples,
+ * rdf_frequent_conditions, rdf_build_capture_groups, rdf_shard_begin or rdf_release_scratch; the accessors return
+ * RDF_ERR_STATE without a view.
+ * rdf_select_cinds leaves the stage and the result as they were, except that it writes the heavy-bits form's deferred
+ * refs into the result buffer as rdf_cind_checksum does; a pending class part stays pending (RDF_T_CEMIT stays 0).
+ * Class rows that a row accessor already expanded are ordinary runs.  Beyond the view the call holds O(captures + runs
+ * + list refs + members) bytes of scratch and 4 B per 2048 refs of the selected dependents' explicit runs.
+ *
+ *   rdf_find_terms           ids[i] = id of term heap[offsets[i], offsets[i + 1]) in the formatting dictionary
+ *                            (rdf_set_dictionary or rdf_set_dictionary_parsed), byte-exact; UINT32_MAX when absent, the
+ *                            smallest id when the dictionary holds duplicates.  n <= 2 * RDF_SEL_MAX_PATTERNS
+ *                            (RDF_ERR_LIMIT); RDF_ERR_STATE without a formatting dictionary.
+ */
+#define RDF_SEL_ANY 0xffffffffu
+#define RDF_SEL_MAX_PATTERNS 256u
+#define RDF_SEL_COUNT_ONLY 1u
+typedef struct {
+    uint32_t codes;   /* bit i admits capture code index i; the index numbers the codes 10 12 14 17 20 21 33 34 35
+                         ascending, as the RDF_CS_SHAPE cells do; 0x1ff = every code */
+    uint32_t value1;  /* term id of the first condition value (order of rdf_decode_capture), or RDF_SEL_ANY */
+    uint32_t value2;  /* term id of the second condition value, or RDF_SEL_ANY; != ANY matches no unary capture */
+} rdf_capture_pattern;
+typedef struct {
+    const rdf_capture_pattern* dep; uint32_t n_dep;   /* n = 0: every capture passes on that side */
+    const rdf_capture_pattern* ref; uint32_t n_ref;
+    uint32_t min_support, max_support;                /* inclusive bounds on the dependent's support; 0 / UINT32_MAX = none */
+    uint32_t flags;
+} rdf_cind_query;
+rdf_status rdf_select_cinds(rdf_ctx* ctx, const rdf_cind_query* q, uint64_t* n_selected, float* ms);
+rdf_status rdf_selected_count(rdf_ctx* ctx, uint64_t* n);
+rdf_status rdf_copy_selected_decoded(rdf_ctx* ctx, uint64_t offset, rdf_cind_row* out, uint64_t count, uint64_t* n_copied);
+rdf_status rdf_format_selected_size(rdf_ctx* ctx, uint64_t offset, uint64_t count, uint64_t* bytes);
+rdf_status rdf_format_selected(rdf_ctx* ctx, uint64_t offset, uint64_t count, char* out, uint64_t cap, uint64_t* bytes);
+rdf_status rdf_find_terms(rdf_ctx* ctx, const char* heap, const uint64_t* offsets, uint32_t n, uint32_t* ids);
+
 /* Device time (ms) of the last call of each stage: [0] fc, [1] groups, [2] cinds. */
 rdf_status rdf_stage_times(rdf_ctx* ctx, float* ms3);
 /* Device time (ms) of each kernel family (RDF_T_*) in the last calls; count <= RDF_NUM_TIMERS. */

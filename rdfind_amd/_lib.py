@@ -38,7 +38,16 @@ EXPORTED_SYMBOLS = (
     "rdf_copy_result_heavy", "rdf_parse_begin", "rdf_parse_chunk", "rdf_parse_end", "rdf_copy_term_heap",
     "rdf_rewrite_terms", "rdf_condition_histogram", "rdf_join_histogram", "rdf_copy_histogram", "rdf_count_literals",
     "rdf_cind_stats_begin", "rdf_cind_stats_add", "rdf_cind_stats_end", "rdf_cind_histogram", "rdf_copy_top_refs",
+    "rdf_select_cinds", "rdf_selected_count", "rdf_copy_selected_decoded", "rdf_format_selected_size",
+    "rdf_format_selected", "rdf_find_terms",
 )
+# result selection (rdf_select_cinds): wildcard value, patterns per side, flags; the code index of a pattern's `codes`
+# bits numbers the capture codes in ascending order
+RDF_SEL_ANY = 0xFFFFFFFF
+RDF_SEL_MAX_PATTERNS = 256
+RDF_SEL_COUNT_ONLY = 1
+SEL_CODES = (10, 12, 14, 17, 20, 21, 33, 34, 35)
+SEL_ALL_CODES = 0x1FF
 # rdf_hist_row kinds of the result statistics (rdf_cind_histogram)
 RDF_CS_SHAPE, RDF_CS_SUPPORT, RDF_CS_REFS, RDF_CS_INDEGREE = 1, 2, 3, 4
 RDF_JH_NO_FIS = 1
@@ -165,6 +174,20 @@ TOP_DTYPE = np.dtype([("capture", "<u4"), ("pad", "<u4"), ("cinds", "<u8")])
 ROW_DTYPE = np.dtype([("dep_capture_type", "<u4"), ("dep_value1", "<u4"), ("dep_value2", "<u4"),
                       ("ref_capture_type", "<u4"), ("ref_value1", "<u4"), ("ref_value2", "<u4"), ("support", "<u4")])
 
+
+
+class CapturePattern(ctypes.Structure):
+    """rdf_capture_pattern (include/rdfind_hip.h)."""
+    _fields_ = [("codes", ctypes.c_uint32), ("value1", ctypes.c_uint32), ("value2", ctypes.c_uint32)]
+
+
+class CindQuery(ctypes.Structure):
+    """rdf_cind_query (include/rdfind_hip.h)."""
+    _fields_ = [("dep", ctypes.POINTER(CapturePattern)), ("n_dep", ctypes.c_uint32),
+                ("ref", ctypes.POINTER(CapturePattern)), ("n_ref", ctypes.c_uint32),
+                ("min_support", ctypes.c_uint32), ("max_support", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
 _lib = None
 
 
@@ -216,6 +239,12 @@ def load():
         "rdf_cind_stats_end": (i32, [P, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_float)]),
         "rdf_cind_histogram": (i32, [P, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_float)]),
         "rdf_copy_top_refs": (i32, [P, P, u64, ctypes.POINTER(u64)]),
+        "rdf_select_cinds": (i32, [P, ctypes.POINTER(CindQuery), ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_float)]),
+        "rdf_selected_count": (i32, [P, ctypes.POINTER(u64)]),
+        "rdf_copy_selected_decoded": (i32, [P, u64, P, u64, ctypes.POINTER(u64)]),
+        "rdf_format_selected_size": (i32, [P, u64, u64, ctypes.POINTER(u64)]),
+        "rdf_format_selected": (i32, [P, u64, u64, P, u64, ctypes.POINTER(u64)]),
+        "rdf_find_terms": (i32, [P, ctypes.c_char_p, P, u32, P]),
         "rdf_frequent_conditions": (i32, [P, u32, ctypes.POINTER(FcStats)]),
         "rdf_build_capture_groups": (i32, [P, ctypes.c_char_p, ctypes.POINTER(GroupStats)]),
         "rdf_discover_cinds": (i32, [P, u32, ctypes.POINTER(CindStats)]),
@@ -565,6 +594,76 @@ class Context:
         self._check(self.lib.rdf_copy_top_refs(self.ptr, out.ctypes.data, out.shape[0], ctypes.byref(got)),
                     "rdf_copy_top_refs")
         return out[: got.value][["capture", "cinds"]]
+
+    # -- result selection ---------------------------------------------------------------------
+    def find_terms(self, terms) -> np.ndarray:
+        """rdf_find_terms: the ids of the given strings in the formatting dictionary (uint32; 0xFFFFFFFF = absent),
+        looked up on the device, RDF_SEL_MAX_PATTERNS * 2 per call."""
+        enc = [t.encode("utf-8") if isinstance(t, str) else bytes(t) for t in terms]
+        ids = np.empty(len(enc), dtype=np.uint32)
+        step = 2 * RDF_SEL_MAX_PATTERNS
+        for b in range(0, len(enc), step):
+            part = enc[b:b + step]
+            heap = b"".join(part)
+            offsets = np.zeros(len(part) + 1, dtype=np.uint64)
+            np.cumsum(np.fromiter((len(e) for e in part), dtype=np.uint64, count=len(part)), out=offsets[1:])
+            buf = ctypes.create_string_buffer(heap, max(len(heap), 1))
+            self._check(self.lib.rdf_find_terms(self.ptr, buf, offsets.ctypes.data, len(part), ids[b:].ctypes.data),
+                        "rdf_find_terms")
+        return ids
+
+    @staticmethod
+    def _patterns(pats):
+        arr = (CapturePattern * max(len(pats), 1))()
+        for i, (cd, v1, v2) in enumerate(pats):
+            arr[i] = CapturePattern(int(cd), int(v1), int(v2))
+        return arr
+
+    def select_cinds(self, dep=(), ref=(), min_support=0, max_support=0xFFFFFFFF, count_only=False) -> int:
+        """rdf_select_cinds on the current result (or page): the CINDs whose dependent matches any of `dep`, whose
+        referenced capture matches any of `ref` (patterns (codes, value1, value2); an empty side admits every capture)
+        and whose support lies in [min_support, max_support].  Returns their number and, unless `count_only`, leaves
+        them as a view for selected_decoded / format_selected; the device time is in ``last_select_ms``."""
+        dep, ref = list(dep), list(ref)
+        da, ra = self._patterns(dep), self._patterns(ref)
+        q = CindQuery(da, len(dep), ra, len(ref), min_support, max_support, RDF_SEL_COUNT_ONLY if count_only else 0)
+        n, ms = ctypes.c_uint64(), ctypes.c_float()
+        self._check(self.lib.rdf_select_cinds(self.ptr, ctypes.byref(q), ctypes.byref(n), ctypes.byref(ms)),
+                    "rdf_select_cinds")
+        self.last_select_ms = float(ms.value)
+        return int(n.value)
+
+    def selected_count(self) -> int:
+        n = ctypes.c_uint64()
+        self._check(self.lib.rdf_selected_count(self.ptr, ctypes.byref(n)), "rdf_selected_count")
+        return int(n.value)
+
+    def selected_decoded(self, offset: int = 0, count: int | None = None) -> np.ndarray:
+        """Rows [offset, offset + count) of the selection view, Cind-shaped (ROW_DTYPE), decoded on the device."""
+        if count is None:
+            count = max(self.selected_count() - offset, 0)
+        out = np.empty(count, dtype=ROW_DTYPE)
+        copied = ctypes.c_uint64()
+        self._check(self.lib.rdf_copy_selected_decoded(self.ptr, offset, out.ctypes.data, count, ctypes.byref(copied)),
+                    "rdf_copy_selected_decoded")
+        return out[: copied.value]
+
+    def format_selected_array(self, offset=0, count=None) -> np.ndarray:
+        """Cind.toString lines of rows [offset, offset + count) of the selection view, as format_array."""
+        if count is None:
+            count = max(self.selected_count() - offset, 0)
+        need = ctypes.c_uint64()
+        self._check(self.lib.rdf_format_selected_size(self.ptr, offset, count, ctypes.byref(need)),
+                    "rdf_format_selected_size")
+        out = np.empty(max(need.value, 1), dtype=np.uint8)
+        got = ctypes.c_uint64()
+        self._check(self.lib.rdf_format_selected(self.ptr, offset, count, out.ctypes.data, need.value, ctypes.byref(got)),
+                    "rdf_format_selected")
+        return out[: got.value]
+
+    def format_selected(self, offset=0, count=None) -> bytes:
+        """As format_selected_array, as bytes."""
+        return self.format_selected_array(offset, count).tobytes()
 
     def cind_stats_times(self):
         """(explicit, class, end) device ms of the last result statistics (rdf_test_cind_stats_times)."""

@@ -4313,6 +4313,7 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_nt_assign_chunk(const u32* __rest
 #include "rewrite.inl"
 #include "histo.inl"
 #include "cindstats.inl"
+#include "select.inl"
 
 }  // namespace rdf
 

@@ -65,6 +65,15 @@ using namespace rdf;
     /* its code index; the 81 shape cells + 2 counters; the sorted top-list keys; the support runs' scanned weights */ \
     /* (rows and sort scratch: the hg* buffers above) */ \
     B(RUN, csnref) B(RUN, csindeg) B(RUN, cscode) B(RUN, cscell) B(RUN, cstop) B(RUN, cstop_tmp) B(RUN, cswsum) \
+    /* result selection (select.inl).  The view: sel_refs, sel_runoff, sel_rundep.  Scratch: the patterns, the dep / */ \
+    /* ref flags per compact capture; per explicit run its candidate weight (then kept flag), scanned weights, kept */ \
+    /* refs, their scan, the kept runs' scan; per tile of candidates the kept refs and their scan; per class the */ \
+    /* selected list's length and start, the selected lists; per member its rows, self rank, scanned rows, kept flag */ \
+    /* and its scan.  rdf_find_terms: the query bytes, offsets and the ids found */ \
+    B(RUN, sel_refs) B(RUN, sel_runoff) B(RUN, sel_rundep) B(RUN, slpat) B(RUN, sldep) B(RUN, slref) B(RUN, slw) \
+    B(RUN, slwoff) B(RUN, slrcnt) B(RUN, slroff) B(RUN, slkpos) B(RUN, sltcnt) B(RUN, sltoff) B(RUN, sllcnt) B(RUN, slloff) \
+    B(RUN, sllist) B(RUN, slmc) B(RUN, slmrank) B(RUN, slmoff) B(RUN, slmflag) B(RUN, slmkpos) B(RUN, slq) B(RUN, slqoff) \
+    B(RUN, slids) \
     /* frequent conditions */ \
     B(RUN, frank) B(RUN, fval) B(RUN, fext) \
     B(RUN, cnt) B(SPARE_FC, tkeys) B(RUN, tcnt) B(RUN, bkeys) B(RUN, bkeys_tmp) B(RUN, lkeys) B(RUN, lvals) B(RUN, flags) \
@@ -199,6 +208,10 @@ struct rdf_ctx : CtxBuffers {
     u64 cs_top_n = 0;
     float cs_ms[3] = {0, 0, 0};  // device time of the open accumulation: explicit passes, class passes, end
     hipEvent_t cs_ev[3] = {};
+    // result selection (select.inl): sel_refs / sel_runoff / sel_rundep hold the view of the last rdf_select_cinds,
+    // sel_rows rows in sel_runs runs; dropped wherever the result it names goes (the resets above, and rdf_next_page)
+    bool sel_valid = false;
+    u64 sel_rows = 0, sel_runs = 0;
     u32 parse_flags = 0;
     u64 pc_n = 0, pc_V = 0, pc_lines = 0, pc_chunks = 0, pc_heap = 0, pc_slots = 0, pc_growths = 0;
     float pc_ms = 0;
@@ -697,7 +710,7 @@ static void release_run_buffers(rdf_ctx* c, u64 n_next, bool always = false) {
     const u64 held = held_bytes(c) - class_bytes(c, BUF_INPUT);
     if (!always && held <= std::max<u64>(4ull << 30, n_next << 10)) return;
     (void)hipStreamSynchronize(c->stream);
-    c->paged = c->cs_open = c->cs_top_valid = false;
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;
     for_each_buf(c, [](DevBuf& b, const BufEntry& e) {
         if (e.cls != BUF_INPUT) b.release();
     });
@@ -716,7 +729,7 @@ rdf_status rdf_release_scratch(rdf_ctx* c) {
     TRY(hv_wait(c, true));
     release_run_buffers(c, 0, true);
     (void)hipGetLastError();  // an out-of-memory failure before this call is not the next call's error
-    c->paged = c->cs_open = c->cs_top_valid = false;
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;
     c->stage = std::min(c->stage, 1);
     return RDF_OK;
 }
@@ -764,7 +777,7 @@ rdf_status rdf_set_triples(rdf_ctx* c, const uint32_t* s, const uint32_t* p, con
     c->n = n;
     c->V = num_terms;
     c->stage = 1;
-    c->paged = c->cs_open = c->cs_top_valid = false;  // a paged run's state belongs to the previous input
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;  // a paged run's state belongs to the previous input
     c->parsed_dict = false;
     c->ingest_sharded = false;
     return RDF_OK;
@@ -783,7 +796,7 @@ rdf_status rdf_set_triples_device(rdf_ctx* c, const uint32_t* s, const uint32_t*
     c->n = n;
     c->V = num_terms;
     c->stage = 1;
-    c->paged = c->cs_open = c->cs_top_valid = false;  // a paged run's state belongs to the previous input
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;  // a paged run's state belongs to the previous input
     c->parsed_dict = false;
     c->ingest_sharded = false;
     return RDF_OK;
@@ -835,7 +848,7 @@ rdf_status rdf_distinct_triples(rdf_ctx* c, uint64_t* n_distinct, float* ms) {
     if (ms) HIP_TRY(c, hipEventElapsedTime(ms, c->ev[6], c->ev[7]));
     c->n = kept;
     c->stage = 1;
-    c->paged = c->cs_open = c->cs_top_valid = false;  // a paged run's state belongs to the previous input
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;  // a paged run's state belongs to the previous input
     if (n_distinct) *n_distinct = kept;
     return RDF_OK;
 }
@@ -947,7 +960,7 @@ rdf_status rdf_parse_ntriples(rdf_ctx* c, const char* text, uint64_t nbytes, uin
     c->n = n;
     c->V = (u32)V;
     c->stage = 1;
-    c->paged = c->cs_open = c->cs_top_valid = false;  // a paged run's state belongs to the previous input
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;  // a paged run's state belongs to the previous input
     c->n_terms_parsed = V;
     c->parsed_dict = true;
     c->ingest_sharded = false;
@@ -1024,7 +1037,7 @@ rdf_status rdf_parse_begin(rdf_ctx* c, uint32_t flags, uint64_t reserve_triples)
     c->ntext.release();
     c->ntheap.release();
     c->stage = 0;
-    c->paged = c->cs_open = c->cs_top_valid = false;
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;
     c->parsed_dict = false;
     c->dict_in_heap = false;
     c->ingest_sharded = false;
@@ -1216,7 +1229,7 @@ rdf_status rdf_parse_end(rdf_ctx* c, rdf_parse_stats* stats) {
     c->n = c->pc_n;
     c->V = (u32)c->pc_V;
     c->stage = 1;
-    c->paged = c->cs_open = c->cs_top_valid = false;
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;
     c->n_terms_parsed = c->pc_V;
     c->parsed_dict = true;
     c->dict_in_heap = true;
@@ -1452,7 +1465,7 @@ rdf_status rdf_rewrite_terms(rdf_ctx* c, uint32_t flags, const char* key_heap, c
     c->p = c->tp.as<u32>();
     c->o = c->to.as<u32>();
     c->stage = 1;
-    c->paged = c->cs_open = c->cs_top_valid = false;
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;
     return RDF_OK;
 }
 
@@ -1882,7 +1895,7 @@ static rdf_status fc_begin(rdf_ctx* c, uint32_t min_support) {
     c->ar_on = false;
     c->n_rules = 0;
     c->class_pending = false;
-    c->paged = c->cs_open = c->cs_top_valid = false;
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;
     c->path_k1 = c->path_k2 = 0;
     c->fcrep = {};
     c->fcrep.traced = c->fc_trace ? 1 : 0;
@@ -2940,7 +2953,7 @@ rdf_status rdf_build_capture_groups(rdf_ctx* c, const char* projection, rdf_grou
     TRY(parse_projection(c, projection, &proj));
     c->rank = 0;
     c->nranks = 1;
-    c->paged = c->cs_open = c->cs_top_valid = false;
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;
     c->n_group_ranges = 1;
     if (c->sw.group_range_records || 9 * c->n >= (1ull << 32)) {
         TRY(g_build_ranges(c, proj, c->sw.group_range_records ? c->sw.group_range_records : auto_range_records(c)));
@@ -3913,7 +3926,7 @@ rdf_status rdf_discover_cinds(rdf_ctx* c, uint32_t flags, rdf_cind_stats* stats)
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(hv_wait(c, true));
     c->res_bits = c->heavy_pending = false;  // (the heavy-bits form: results of d_emit_rest / d_page_emit only)
-    c->paged = c->cs_open = c->cs_top_valid = false;
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;
     // test hook (RDFIND_TEST_OOM_DISCOVERY=1): the unpaged discovery reports RDF_ERR_OOM at once, so a caller's
     // fallback to pages runs on small inputs
     if (c->sw.test_oom_discovery) return fail(c, RDF_ERR_OOM, "test hook: the unpaged discovery runs out of memory");
@@ -4205,7 +4218,7 @@ rdf_status rdf_discover_cinds_paged(rdf_ctx* c, uint32_t flags, uint64_t page_by
     c->pg_pages = 0;
     c->pg_unary_done = false;
     c->paged = true;
-    c->cs_open = c->cs_top_valid = false;  // (a new capture table)
+    c->cs_open = c->cs_top_valid = c->sel_valid = false;  // (a new capture table)
     HIP_TRY(c, hipEventRecord(c->ev[5], st));
     HIP_TRY(c, hipStreamSynchronize(st));
     HIP_TRY(c, hipEventElapsedTime(&c->stage_ms[2], c->ev[4], c->ev[5]));
@@ -4230,6 +4243,7 @@ rdf_status rdf_next_page(rdf_ctx* c, uint32_t* done, uint64_t* first_dep, uint64
     if (!c || !done) return RDF_ERR_ARG;
     if (!c->paged || c->stage < 3) return fail(c, RDF_ERR_STATE, "rdf_discover_cinds_paged must be called first");
     HIP_TRY(c, hipSetDevice(c->device));
+    c->sel_valid = false;  // a selection view names the page it was taken from
     CindView v = make_view(c, c->pg_flags);
     v.eoff = c->eoff.as<u64>();
     v.epairs = c->epairs.as<u64>();
@@ -5258,7 +5272,7 @@ static rdf_status sh_phase24(rdf_ctx* c, rdf_exchange* req) {
     c->parsed_dict = false;
     c->ingest_sharded = true;
     c->stage = 1;
-    c->paged = c->cs_open = c->cs_top_valid = false;  // a paged run's state belongs to the previous input
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;  // a paged run's state belongs to the previous input
     memset(req, 0, sizeof(*req));
     req->op = RDF_X_DONE;
     c->sh_phase = 9;
@@ -5364,7 +5378,7 @@ rdf_status rdf_shard_begin(rdf_ctx* c, uint32_t rank, uint32_t nranks, uint32_t 
     c->x_imported = true;
     c->spare_x = false;  // (a run that failed between phases 14 and 1 left them marked)
     c->stage = std::min(c->stage, 1);
-    c->paged = c->cs_open = c->cs_top_valid = false;
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;
     return RDF_OK;
 }
 
@@ -5384,7 +5398,7 @@ rdf_status rdf_shard_parse_begin(rdf_ctx* c, uint32_t rank, uint32_t nranks, con
     c->sh_phase = 20;
     c->x_imported = true;
     c->stage = 0;  // no usable triples until the global ids arrive
-    c->paged = c->cs_open = c->cs_top_valid = false;
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;
     if (n_triples) *n_triples = n;
     return RDF_OK;
 }
@@ -5800,24 +5814,38 @@ rdf_status rdf_copy_result_raw(rdf_ctx* c, uint32_t* refs, uint64_t* runoff, uin
     return RDF_OK;
 }
 
-// Cind-shaped rows on the device (decode kernel), copied to the caller in chunks
+// where a decode or formatter launch reads its rows: the result (after materialize) or a selection view (select.inl)
+struct RowSource {
+    const u32* refs;
+    const u64* runoff;
+    const u32* rundep;
+    u64 R;
+};
+static RowSource result_rows(const rdf_ctx* c) { return {c->out_ptr, c->runoff.as<u64>(), c->rundep.as<u32>(), c->n_runs}; }
+
+// Cind-shaped rows [offset, offset + m) of `src` on the device (decode kernel), copied to the caller in chunks
+static rdf_status decode_rows(rdf_ctx* c, const RowSource& src, u64 offset, u64 m, rdf_cind_row* out) {
+    const u64 kChunk = 1ull << 22;
+    if (m) ENSURE(c, drows, std::min<u64>(m, kChunk) * sizeof(rdf_cind_row));
+    for (u64 b = 0; b < m; b += kChunk) {
+        const u64 k = std::min(kChunk, m - b);
+        hipLaunchKernelGGL(k_decode_rows, dim3(grid_for(k, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, c->stream, src.refs,
+                           offset + b, k, src.runoff, src.rundep, src.R, c->fext.as<u32>(), c->csup.as<u32>(),
+                           c->V ? c->V : 1u, c->bkeys.as<u64>(), c->drows.as<u32>());
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(out + b, c->drows.p, k * sizeof(rdf_cind_row), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));  // drows is reused by the next chunk
+    }
+    return RDF_OK;
+}
+
 rdf_status rdf_copy_cinds_decoded(rdf_ctx* c, uint64_t offset, rdf_cind_row* out, uint64_t count, uint64_t* n_copied) {
     if (!c || (count && !out)) return RDF_ERR_ARG;
     if (c->stage < 4) return fail(c, RDF_ERR_STATE, "rdf_discover_cinds must be called first");
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(materialize(c));
     const u64 m = offset >= c->n_out ? 0 : std::min<u64>(count, c->n_out - offset);
-    const u64 kChunk = 1ull << 22;
-    if (m) ENSURE(c, drows, std::min<u64>(m, kChunk) * sizeof(rdf_cind_row));
-    for (u64 b = 0; b < m; b += kChunk) {
-        const u64 k = std::min(kChunk, m - b);
-        hipLaunchKernelGGL(k_decode_rows, dim3(grid_for(k, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, c->stream, c->out_ptr,
-                           offset + b, k, c->runoff.as<u64>(), c->rundep.as<u32>(), c->n_runs, c->fext.as<u32>(),
-                           c->csup.as<u32>(), c->V ? c->V : 1u, c->bkeys.as<u64>(), c->drows.as<u32>());
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(out + b, c->drows.p, k * sizeof(rdf_cind_row), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));  // drows is reused by the next chunk
-    }
+    TRY(decode_rows(c, result_rows(c), offset, m, out));
     if (n_copied) *n_copied = m;
     return RDF_OK;
 }
@@ -5911,19 +5939,31 @@ static rdf_status ensure_capstr(rdf_ctx* c) {
     return RDF_OK;
 }
 
-// line offsets of result rows [offset, offset + m) -> floff, *bytes
-static rdf_status fmt_prepare(rdf_ctx* c, u64 offset, u64 m, u64* bytes) {
+// line offsets of rows [offset, offset + m) of `src` -> floff, *bytes
+static rdf_status fmt_prepare(rdf_ctx* c, const RowSource& src, u64 offset, u64 m, u64* bytes) {
     hipStream_t st = c->stream;
-    TRY(materialize(c));
     TRY(ensure_capstr(c));
     ENSURE(c, flen, std::max<u64>(m, 1) * 4);
     ENSURE(c, floff, (m + 1) * 8);
     if (m)
-        hipLaunchKernelGGL(k_fmt_len, dim3(grid_for(m, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->out_ptr, offset, m,
-                           c->runoff.as<u64>(), c->rundep.as<u32>(), c->n_runs, c->csoff.as<u64>(), c->csup.as<u32>(),
-                           c->flen.as<u32>());
+        hipLaunchKernelGGL(k_fmt_len, dim3(grid_for(m, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, src.refs, offset, m,
+                           src.runoff, src.rundep, src.R, c->csoff.as<u64>(), c->csup.as<u32>(), c->flen.as<u32>());
     HIP_TRY(c, exclusive_scan_u32_u64(c->ws, c->flen.as<u32>(), c->floff.as<u64>(), m, c->floff.as<u64>() + m, st));
     return read_u64(c, c->floff.as<u64>() + m, bytes);
+}
+
+// the lines of those rows (fmt_prepare has run and found `total` bytes) into the caller's buffer
+static rdf_status fmt_write(rdf_ctx* c, const RowSource& src, u64 offset, u64 m, u64 total, char* out) {
+    ENSURE(c, fbuf, std::max<u64>(total, 1));
+    if (m)
+        hipLaunchKernelGGL(k_fmt_write, dim3(grid_for((m + RDF_WAVE - 1) / RDF_WAVE, RDF_WAVES_PER_BLOCK, kGrid)),
+                           dim3(RDF_BLOCK), 0, c->stream, src.refs, offset, m, src.runoff, src.rundep, src.R,
+                           c->csoff.as<u64>(), c->cstr.as<char>(), c->csup.as<u32>(), c->floff.as<u64>(),
+                           c->fbuf.as<char>());
+    HIP_TRY(c, hipGetLastError());
+    if (total) HIP_TRY(c, hipMemcpyAsync(out, c->fbuf.p, total, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return RDF_OK;
 }
 
 rdf_status rdf_format_size(rdf_ctx* c, uint64_t offset, uint64_t count, uint64_t* bytes) {
@@ -5931,7 +5971,8 @@ rdf_status rdf_format_size(rdf_ctx* c, uint64_t offset, uint64_t count, uint64_t
     if (c->stage < 4) return fail(c, RDF_ERR_STATE, "rdf_discover_cinds must be called first");
     HIP_TRY(c, hipSetDevice(c->device));
     const u64 m = offset >= c->n_out ? 0 : std::min<u64>(count, c->n_out - offset);
-    return fmt_prepare(c, offset, m, (u64*)bytes);
+    TRY(materialize(c));
+    return fmt_prepare(c, result_rows(c), offset, m, (u64*)bytes);
 }
 
 rdf_status rdf_format_cinds(rdf_ctx* c, uint64_t offset, uint64_t count, char* out, uint64_t cap, uint64_t* bytes) {
@@ -5940,19 +5981,11 @@ rdf_status rdf_format_cinds(rdf_ctx* c, uint64_t offset, uint64_t count, char* o
     HIP_TRY(c, hipSetDevice(c->device));
     const u64 m = offset >= c->n_out ? 0 : std::min<u64>(count, c->n_out - offset);
     u64 total = 0;
-    TRY(fmt_prepare(c, offset, m, &total));
+    TRY(materialize(c));
+    TRY(fmt_prepare(c, result_rows(c), offset, m, &total));
     *bytes = total;
     if (total > cap) return fail(c, RDF_ERR_ARG, "output buffer too small (see *bytes)");
-    ENSURE(c, fbuf, std::max<u64>(total, 1));
-    if (m)
-        hipLaunchKernelGGL(k_fmt_write, dim3(grid_for((m + RDF_WAVE - 1) / RDF_WAVE, RDF_WAVES_PER_BLOCK, kGrid)),
-                           dim3(RDF_BLOCK), 0, c->stream, c->out_ptr, offset, m, c->runoff.as<u64>(), c->rundep.as<u32>(),
-                           c->n_runs, c->csoff.as<u64>(), c->cstr.as<char>(), c->csup.as<u32>(), c->floff.as<u64>(),
-                           c->fbuf.as<char>());
-    HIP_TRY(c, hipGetLastError());
-    if (total) HIP_TRY(c, hipMemcpyAsync(out, c->fbuf.p, total, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return RDF_OK;
+    return fmt_write(c, result_rows(c), offset, m, total, out);
 }
 
 rdf_status rdf_decode_capture(rdf_ctx* c, uint32_t capture, uint32_t* code, uint32_t* value1, uint32_t* value2) {
@@ -6423,6 +6456,250 @@ rdf_status rdf_copy_top_refs(rdf_ctx* c, rdf_top_ref* out, uint64_t cap, uint64_
     }
     if (n_copied) *n_copied = m;
     return RDF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Result selection (select.inl): rdf_select_cinds, the view's accessors, rdf_find_terms.  Buffers of their own (sel_* the
+// view, sl* scratch), the statistics' timing events (both calls wait for the stream before they return): no pipeline
+// state changes, and a pending class part stays pending.
+
+// scan of n u32 counts into off[0, n] and the total back to the host
+static rdf_status sel_scan(rdf_ctx* c, const u32* in, u64* off, u64 n, u64* total) {
+    HIP_TRY(c, exclusive_scan_u32_u64(c->ws, in, off, n, off + n, c->stream));
+    return read_u64(c, off + n, total);
+}
+
+rdf_status rdf_select_cinds(rdf_ctx* c, const rdf_cind_query* q, uint64_t* n_selected, float* ms) {
+    if (!c || !q || !n_selected) return RDF_ERR_ARG;
+    TRY(cs_single_gpu(c, "rdf_select_cinds"));
+    if (c->stage < 4) return fail(c, RDF_ERR_STATE, "no current result: rdf_discover_cinds or rdf_next_page comes first");
+    if (q->n_dep > RDF_SEL_MAX_PATTERNS || q->n_ref > RDF_SEL_MAX_PATTERNS)
+        return fail(c, RDF_ERR_LIMIT, "at most " + std::to_string(RDF_SEL_MAX_PATTERNS) + " patterns on a side");
+    if ((q->n_dep && !q->dep) || (q->n_ref && !q->ref)) return fail(c, RDF_ERR_ARG, "patterns counted but not given");
+    if (q->min_support > q->max_support) return fail(c, RDF_ERR_ARG, "min_support exceeds max_support");
+    if (q->flags & ~RDF_SEL_COUNT_ONLY) return fail(c, RDF_ERR_ARG, "unknown selection flags");
+    std::vector<rdf_capture_pattern> pats(q->dep, q->dep + q->n_dep);
+    pats.insert(pats.end(), q->ref, q->ref + q->n_ref);
+    for (const auto& p : pats)
+        if (p.codes & ~0x1ffu) return fail(c, RDF_ERR_ARG, "pattern codes outside 0x1ff");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    c->sel_valid = false;
+    TRY(materialize_heavy(c));
+    // the rows that lie in `out` and their runs, as rdf_cind_stats_add takes them; a pending class part is selected
+    // from its compact form
+    const bool pending = c->class_pending && c->pend_NT && c->n_classes;
+    const u64 nrows = c->class_pending ? c->n_out - c->n_class_out : c->n_out;
+    const u64 R = c->class_pending ? c->n_runs_explicit : c->n_runs;
+    const u32 C = c->C;
+    const unsigned char* depsel = nullptr;
+    const unsigned char* refsel = nullptr;
+    HIP_TRY(c, hipEventRecord(c->cs_ev[0], st));
+    if (C) {
+        ENSURE(c, slpat, std::max<size_t>(pats.size(), 1) * sizeof(rdf_capture_pattern));
+        ENSURE(c, sldep, C);
+        ENSURE(c, slref, C);
+        if (!pats.empty())
+            HIP_TRY(c, ctx_copy(c, c->slpat.p, pats.data(), pats.size() * sizeof(rdf_capture_pattern), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_sel_flags, dim3(grid_for(C, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->fext.as<u32>(), C,
+                           c->V ? c->V : 1u, c->bkeys.as<u64>(), c->csup.as<u32>(), c->slpat.as<rdf_capture_pattern>(),
+                           q->n_dep, q->n_ref, q->min_support, q->max_support, c->sldep.as<unsigned char>(),
+                           c->slref.as<unsigned char>());
+        HIP_TRY(c, hipGetLastError());
+        depsel = c->sldep.as<unsigned char>();
+        refsel = c->slref.as<unsigned char>();
+    }
+    // explicit part: count
+    u64 S = 0, T = 0, Esel = 0, Kexp = 0;
+    if (C && nrows && R) {
+        ENSURE(c, slw, R * 4);
+        ENSURE(c, slwoff, (R + 1) * 8);
+        hipLaunchKernelGGL(k_sel_run_len, dim3(grid_for(R, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->runoff.as<u64>(),
+                           c->rundep.as<u32>(), R, depsel, c->slw.as<u32>());
+        HIP_TRY(c, hipGetLastError());
+        TRY(sel_scan(c, c->slw.as<u32>(), c->slwoff.as<u64>(), R, &S));
+    }
+    if (S) {
+        T = (S + SEL_TILE - 1) / SEL_TILE;
+        ENSURE(c, slrcnt, R * 4);
+        ENSURE(c, slroff, (R + 1) * 8);
+        ENSURE(c, slkpos, (R + 1) * 8);
+        ENSURE(c, sltcnt, T * 4);
+        ENSURE(c, sltoff, (T + 1) * 8);
+        HIP_TRY(c, hipMemsetAsync(c->slrcnt.p, 0, R * 4, st));
+        hipLaunchKernelGGL(k_sel_count, dim3(vgrid(T)), dim3(RDF_BLOCK), 0, st, c->out_ptr, c->runoff.as<u64>(),
+                           c->slwoff.as<u64>(), R, S, refsel, c->slrcnt.as<u32>(), c->sltcnt.as<u32>());
+        HIP_TRY(c, hipGetLastError());
+        TRY(sel_scan(c, c->slrcnt.as<u32>(), c->slroff.as<u64>(), R, &Esel));
+        if (Esel && !(q->flags & RDF_SEL_COUNT_ONLY)) {
+            hipLaunchKernelGGL(k_sel_nonzero, dim3(grid_for(R, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->slrcnt.as<u32>(),
+                               R, c->slw.as<u32>());  // (the weights are scanned: slw is free)
+            HIP_TRY(c, hipGetLastError());
+            TRY(sel_scan(c, c->slw.as<u32>(), c->slkpos.as<u64>(), R, &Kexp));
+            u64 check = 0;
+            TRY(sel_scan(c, c->sltcnt.as<u32>(), c->sltoff.as<u64>(), T, &check));
+            if (check != Esel) return fail(c, RDF_ERR_HIP, "selection: the tile counts disagree with the run counts");
+        }
+    }
+    // pending class part: count
+    const u64 ncls = pending ? c->n_classes : 0, nmem = pending ? c->n_class_members : 0;
+    u64 LS = 0, Sc = 0, Kc = 0;
+    if (C && ncls && nmem) {
+        ENSURE(c, sllcnt, ncls * 4);
+        ENSURE(c, slloff, (ncls + 1) * 8);
+        hipLaunchKernelGGL(k_sel_class_count, dim3(vgrid(std::min<u64>(ncls, kGrid))), dim3(RDF_BLOCK), 0, st, (u32)ncls,
+                           c->coff.as<u64>(), c->cchoff.as<u64>(), c->lwoff.as<u64>(), c->clists.as<u32>(), c->ckeys.as<u64>(),
+                           depsel, refsel, c->sllcnt.as<u32>());
+        HIP_TRY(c, hipGetLastError());
+        TRY(sel_scan(c, c->sllcnt.as<u32>(), c->slloff.as<u64>(), ncls, &LS));
+    }
+    if (LS) {
+        ENSURE(c, sllist, LS * 4);
+        ENSURE(c, slmc, nmem * 4);
+        ENSURE(c, slmrank, nmem * 4);
+        ENSURE(c, slmoff, (nmem + 1) * 8);
+        hipLaunchKernelGGL(k_sel_class_compact, dim3(vgrid(std::min<u64>(ncls, kGrid))), dim3(RDF_BLOCK), 0, st, (u32)ncls,
+                           c->cchoff.as<u64>(), c->lwoff.as<u64>(), c->clists.as<u32>(), refsel, c->slloff.as<u64>(),
+                           c->sllist.as<u32>());
+        hipLaunchKernelGGL(k_sel_member_rows, dim3(grid_for(nmem, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->ckeys.as<u64>(),
+                           nmem, c->cself.as<u32>(), depsel, refsel, c->slloff.as<u64>(), c->sllist.as<u32>(),
+                           c->slmc.as<u32>(), c->slmrank.as<u32>());
+        HIP_TRY(c, hipGetLastError());
+        TRY(sel_scan(c, c->slmc.as<u32>(), c->slmoff.as<u64>(), nmem, &Sc));
+        if (Sc && !(q->flags & RDF_SEL_COUNT_ONLY)) {
+            ENSURE(c, slmflag, nmem * 4);
+            ENSURE(c, slmkpos, (nmem + 1) * 8);
+            hipLaunchKernelGGL(k_sel_nonzero, dim3(grid_for(nmem, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->slmc.as<u32>(),
+                               nmem, c->slmflag.as<u32>());
+            HIP_TRY(c, hipGetLastError());
+            TRY(sel_scan(c, c->slmflag.as<u32>(), c->slmkpos.as<u64>(), nmem, &Kc));
+        }
+    }
+    const u64 rows = Esel + Sc, runs = Kexp + Kc;
+    if (!(q->flags & RDF_SEL_COUNT_ONLY)) {
+        // the view, all three buffers or none: a failure names what the view needs
+        const u64 need = std::max<u64>(rows, 1) * 4 + (runs + 1) * 8 + std::max<u64>(runs, 1) * 4;
+        rdf_status rs = ensure_buf(c, &c->sel_refs, (size_t)(std::max<u64>(rows, 1) * 4), "allocating sel_refs");
+        if (rs == RDF_OK) rs = ensure_buf(c, &c->sel_runoff, (size_t)((runs + 1) * 8), "allocating sel_runoff");
+        if (rs == RDF_OK) rs = ensure_buf(c, &c->sel_rundep, (size_t)(std::max<u64>(runs, 1) * 4), "allocating sel_rundep");
+        if (rs != RDF_OK) {
+            c->sel_refs.release();
+            c->sel_runoff.release();
+            c->sel_rundep.release();
+            return rs == RDF_ERR_OOM ? fail(c, rs, "the selection view of " + std::to_string(rows) + " rows in " +
+                                                       std::to_string(runs) + " runs needs " + std::to_string(need) +
+                                                       " bytes of device memory")
+                                     : rs;
+        }
+        u64* vrunoff = c->sel_runoff.as<u64>();
+        u32* vrundep = c->sel_rundep.as<u32>();
+        if (Esel) {
+            hipLaunchKernelGGL(k_sel_write, dim3(vgrid(T)), dim3(RDF_BLOCK), 0, st, c->out_ptr, c->runoff.as<u64>(),
+                               c->slwoff.as<u64>(), R, S, refsel, c->sltoff.as<u64>(), c->sel_refs.as<u32>());
+            hipLaunchKernelGGL(k_sel_runs, dim3(grid_for(R, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->slrcnt.as<u32>(),
+                               c->slroff.as<u64>(), c->slkpos.as<u64>(), c->rundep.as<u32>(), (const u64*)nullptr, R, 0ull, 0ull,
+                               vrunoff, vrundep);
+        }
+        if (Sc) {
+            hipLaunchKernelGGL(k_sel_class_emit, dim3(grid_for(Sc, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->ckeys.as<u64>(),
+                               nmem, c->slmoff.as<u64>(), Sc, c->slmrank.as<u32>(), c->slloff.as<u64>(), c->sllist.as<u32>(),
+                               c->sel_refs.as<u32>() + Esel);
+            hipLaunchKernelGGL(k_sel_runs, dim3(grid_for(nmem, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->slmc.as<u32>(),
+                               c->slmoff.as<u64>(), c->slmkpos.as<u64>(), (const u32*)nullptr, c->ckeys.as<u64>(), nmem, Esel,
+                               Kexp, vrunoff, vrundep);
+        }
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(vrunoff + runs, &rows, 8, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(c, hipEventRecord(c->cs_ev[1], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (ms) HIP_TRY(c, hipEventElapsedTime(ms, c->cs_ev[0], c->cs_ev[1]));
+    if (!(q->flags & RDF_SEL_COUNT_ONLY)) {
+        c->sel_rows = rows;
+        c->sel_runs = runs;
+        c->sel_valid = true;
+    }
+    *n_selected = rows;
+    return RDF_OK;
+}
+
+static rdf_status sel_view(rdf_ctx* c, const char* what, RowSource* src) {
+    TRY(cs_single_gpu(c, what));
+    if (!c->sel_valid || c->stage < 4)
+        return fail(c, RDF_ERR_STATE, std::string(what) + ": no selection view (rdf_select_cinds comes first)");
+    *src = {c->sel_refs.as<u32>(), c->sel_runoff.as<u64>(), c->sel_rundep.as<u32>(), c->sel_runs};
+    return RDF_OK;
+}
+
+rdf_status rdf_selected_count(rdf_ctx* c, uint64_t* n) {
+    if (!c || !n) return RDF_ERR_ARG;
+    RowSource src;
+    TRY(sel_view(c, "rdf_selected_count", &src));
+    *n = c->sel_rows;
+    return RDF_OK;
+}
+
+rdf_status rdf_copy_selected_decoded(rdf_ctx* c, uint64_t offset, rdf_cind_row* out, uint64_t count, uint64_t* n_copied) {
+    if (!c || (count && !out)) return RDF_ERR_ARG;
+    RowSource src;
+    TRY(sel_view(c, "rdf_copy_selected_decoded", &src));
+    HIP_TRY(c, hipSetDevice(c->device));
+    const u64 m = offset >= c->sel_rows ? 0 : std::min<u64>(count, c->sel_rows - offset);
+    TRY(decode_rows(c, src, offset, m, out));
+    if (n_copied) *n_copied = m;
+    return RDF_OK;
+}
+
+rdf_status rdf_format_selected_size(rdf_ctx* c, uint64_t offset, uint64_t count, uint64_t* bytes) {
+    if (!c || !bytes) return RDF_ERR_ARG;
+    RowSource src;
+    TRY(sel_view(c, "rdf_format_selected_size", &src));
+    HIP_TRY(c, hipSetDevice(c->device));
+    const u64 m = offset >= c->sel_rows ? 0 : std::min<u64>(count, c->sel_rows - offset);
+    return fmt_prepare(c, src, offset, m, (u64*)bytes);
+}
+
+rdf_status rdf_format_selected(rdf_ctx* c, uint64_t offset, uint64_t count, char* out, uint64_t cap, uint64_t* bytes) {
+    if (!c || !bytes || (cap && !out)) return RDF_ERR_ARG;
+    RowSource src;
+    TRY(sel_view(c, "rdf_format_selected", &src));
+    HIP_TRY(c, hipSetDevice(c->device));
+    const u64 m = offset >= c->sel_rows ? 0 : std::min<u64>(count, c->sel_rows - offset);
+    u64 total = 0;
+    TRY(fmt_prepare(c, src, offset, m, &total));
+    *bytes = total;
+    if (total > cap) return fail(c, RDF_ERR_ARG, "output buffer too small (see *bytes)");
+    return fmt_write(c, src, offset, m, total, out);
+}
+
+rdf_status rdf_find_terms(rdf_ctx* c, const char* heap, const uint64_t* offsets, uint32_t n, uint32_t* ids) {
+    if (!c || (n && (!offsets || !ids))) return RDF_ERR_ARG;
+    if (n > SEL_FT_MAX) return fail(c, RDF_ERR_LIMIT, "at most " + std::to_string(SEL_FT_MAX) + " terms in one call");
+    if (!c->dtoff.p || !c->dheap.p)
+        return fail(c, RDF_ERR_STATE, "no formatting dictionary: rdf_set_dictionary or rdf_set_dictionary_parsed comes first");
+    if (!n) return RDF_OK;
+    for (u32 i = 0; i < n; ++i)
+        if (offsets[i] > offsets[i + 1]) return fail(c, RDF_ERR_ARG, "term offsets must ascend");
+    const u64 q0 = offsets[0], qbytes = offsets[n] - q0;
+    if (qbytes && !heap) return RDF_ERR_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    ENSURE(c, slq, std::max<u64>(qbytes, 1));
+    ENSURE(c, slqoff, (n + 1ull) * 8);
+    ENSURE(c, slids, (u64)n * 4);
+    std::vector<u64> rel(n + 1);
+    for (u32 i = 0; i <= n; ++i) rel[i] = offsets[i] - q0;
+    if (qbytes) HIP_TRY(c, ctx_copy(c, c->slq.p, heap + q0, qbytes, hipMemcpyHostToDevice));
+    HIP_TRY(c, ctx_copy(c, c->slqoff.p, rel.data(), (n + 1ull) * 8, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemsetAsync(c->slids.p, 0xff, (u64)n * 4, st));
+    if (c->dict_terms)
+        hipLaunchKernelGGL(k_find_terms, dim3(grid_for(c->dict_terms, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st,
+                           c->dheap.as<char>(), c->dtoff.as<u64>(), c->dict_terms, c->slq.as<char>(), c->slqoff.as<u64>(), n,
+                           c->slids.as<u32>());
+    HIP_TRY(c, hipGetLastError());
+    return ctx_copy(c, ids, c->slids.p, (u64)n * 4, hipMemcpyDeviceToHost) == hipSuccess
+               ? RDF_OK
+               : fail(c, RDF_ERR_HIP, "rdf_find_terms: copying the ids");
 }
 
 rdf_status rdf_kernel_times(rdf_ctx* c, float* ms, int count) {

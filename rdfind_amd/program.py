@@ -11,6 +11,9 @@ middle stages run on the GPU through the C ABI (``include/rdfind_hip.h``); there
 ``--cind-statistics [K]`` (build-specific) prints what the result contains before ``Detected n CINDs.``: the CINDs per
 shape and per support, the dependents per number of references, the captures per in-degree and the K most referenced
 captures (``rdf_cind_histogram`` / ``rdf_cind_stats_*``, on the device, the class part of the result unexpanded).
+``--select-dep`` / ``--select-ref`` / ``--select-support`` / ``--select-count`` (build-specific) restrict what is written,
+collected and returned to the CINDs whose dependent, referenced capture and support match (``rdf_select_cinds``, on the
+device, the class part unexpanded); ``Selected m CINDs.`` is printed before the place of ``Detected n CINDs.``.
 
 Flag names follow ``RDFind.Parameters`` (RDFind.scala:639-721).  Flags that only change how Flink
 executes (and not the result) are accepted and ignored; flags whose semantics are out of scope for
@@ -79,6 +82,16 @@ def build_parser():
                     help="build-specific: print the result's statistics before the CIND count: CINDs per shape and per "
                          "support, dependents per number of references, captures per in-degree, and the K (default 10) "
                          "most referenced captures")
+    ap.add_argument("--select-dep", action="append", default=None, metavar="PATTERN",
+                    help="build-specific: write only the CINDs whose dependent capture matches PATTERN (repeatable: any "
+                         "of them).  PATTERN is a capture as the output prints it, s[p=<iri>] or o[s=<a>,p=\"b\"]; a "
+                         "value or the projection may be *, and a bare term selects every capture that names it")
+    ap.add_argument("--select-ref", action="append", default=None, metavar="PATTERN",
+                    help="build-specific: as --select-dep, for the referenced capture")
+    ap.add_argument("--select-support", default=None, metavar="LO[:HI]",
+                    help="build-specific: write only the CINDs whose support lies in [LO, HI]")
+    ap.add_argument("--select-count", action="store_true",
+                    help="build-specific: count the selected CINDs only; nothing is formatted or written")
     ap.add_argument("--ingest-window", type=int, default=1 << 30, metavar="BYTES",
                     help="build-specific: an input larger than this is parsed on the device in windows of whole lines "
                          "of at most this many bytes, so neither the host nor the GPU holds the whole text")
@@ -120,6 +133,14 @@ class RDFind:
             # the result statistics read one GPU's result; a rank holds its own dependents only, and a capture's
             # in-degree would need a collective over capture ids
             raise NotImplementedError("--cind-statistics with -dop > 1")
+        self.selection = None  # (dep pattern specs, ref pattern specs, lo, hi) of the --select-* flags
+        if self.args.select_dep or self.args.select_ref or self.args.select_support is not None or self.args.select_count:
+            if self.args.dop > 1:
+                # the selection reads one GPU's result; a rank holds its own dependents only
+                raise NotImplementedError("--select-dep / --select-ref / --select-support / --select-count with -dop > 1")
+            lo, hi = parse_support_range(self.args.select_support)
+            self.selection = ([parse_capture_pattern(t) for t in self.args.select_dep or []],
+                              [parse_capture_pattern(t) for t in self.args.select_ref or []], lo, hi)
         self.timings = {}
         self.rewrite_stats = None  # rdf_rewrite_stats of the device term rewrite (--prefixes / --asciify-triples)
 
@@ -152,6 +173,8 @@ class RDFind:
                 raise NotImplementedError("--create-join-histogram with -dop > 1")
             if a.cind_statistics is not None:
                 raise NotImplementedError("--cind-statistics with -dop > 1")
+            if self.selection is not None:
+                raise NotImplementedError("--select-* with -dop > 1")
             import torch
             import torch.distributed as dist  # the ranks' exchange (rdfind_amd/distributed.py)
             if not dist.is_initialized():  # RDFIND_DIST_BACKEND=gloo: host-staged exchange (rehearsals on one GPU)
@@ -301,7 +324,9 @@ class RDFind:
         formatted and written before the next one is computed.
         --cind-statistics: taken before any formatting (unpaged), so the class part is counted unexpanded and a result
         that is neither written nor kept as lines is never expanded; or accumulated page by page.  Printed to out
-        before the lines and the count."""
+        before the lines and the count.
+        --select-*: the lines written, collected and returned are those of the selection (rdf_select_cinds on the result
+        or on each page, the class part unexpanded); the statistics still describe the whole result."""
         a = self.args
         ctx.sync()
         self.timings["discover"] = time.time() - t1
@@ -315,6 +340,7 @@ class RDFind:
             ctx.set_dictionary_parsed()  # device dictionary straight into the formatter
         else:
             ctx.set_dictionary(dic.terms)
+        query = None if self.selection is None else self._resolve_selection(ctx)  # (the dictionary is set)
         keep_all = a.collect_result or a.debug_level >= 3
         lines = []
         f = None
@@ -324,13 +350,20 @@ class RDFind:
         n = 0
         stats_k = a.cind_statistics
         stat_rows = top = None
+        n_sel = 0
         try:
             if page_bytes is None:
                 n = ctx.cind_count()
                 if stats_k is not None:
                     stat_rows, top = ctx.cind_histogram(), ctx.top_refs(stats_k)
-                lines = lines if n <= KEEP_LINES_MAX or keep_all else None
-                self._format_result(ctx, n, f, lines)
+                if query is not None:
+                    n_sel = ctx.select_cinds(count_only=a.select_count, **query)
+                    lines = lines if n_sel <= KEEP_LINES_MAX or keep_all else None
+                    if not a.select_count:
+                        self._format_result(ctx, n_sel, f, lines, ctx.format_selected_array)
+                else:
+                    lines = lines if n <= KEEP_LINES_MAX or keep_all else None
+                    self._format_result(ctx, n, f, lines)
             else:
                 pages = 0
                 ctx.discover_cinds_paged(a.clean_implied, a.traversal_strategy, page_bytes)
@@ -342,9 +375,15 @@ class RDFind:
                     m = ctx.cind_count()
                     n += m
                     pages += 1
-                    if lines is not None and n > KEEP_LINES_MAX and not keep_all:
+                    if query is not None:
+                        m = ctx.select_cinds(count_only=a.select_count, **query)
+                        n_sel += m
+                    if lines is not None and (n if query is None else n_sel) > KEEP_LINES_MAX and not keep_all:
                         lines = None
-                    self._format_result(ctx, m, f, lines)
+                    if query is None:
+                        self._format_result(ctx, m, f, lines)
+                    elif not a.select_count:
+                        self._format_result(ctx, m, f, lines, ctx.format_selected_array)
                 if stats_k is not None:
                     stat_rows, top = ctx.cind_stats_end(), ctx.top_refs(stats_k)
                 self.stats["pages"] = pages
@@ -366,13 +405,28 @@ class RDFind:
         if stat_rows is not None:
             for ln in cind_statistics_lines(stat_rows.tolist(), top.tolist(), *self._capture_lookup(ctx, top["capture"])):
                 print(ln, file=out)
-        if a.collect_result or a.debug_level >= 3:
+        if (a.collect_result or a.debug_level >= 3) and not a.select_count:
             for ln in lines:
                 print(ln, file=out)
-        if not a.output and not a.collect_result:
+        if query is not None:
+            print(f"Selected {n_sel} CINDs.", file=out)
+            self.n_selected = n_sel
+        if not a.output and not a.collect_result and not a.select_count:
             print(f"Detected {n} CINDs.", file=out)
         self.n_cinds = n
         return lines
+
+    def _resolve_selection(self, ctx):
+        """The --select-* flags as select_cinds arguments: the patterns' terms looked up in the formatting dictionary
+        on the device (rdf_find_terms).  A pattern naming a term the dictionary lacks matches nothing."""
+        dep_specs, ref_specs, lo, hi = self.selection
+        terms = sorted({t for spec in dep_specs + ref_specs for _, t1, t2 in spec for t in (t1, t2) if t is not None})
+        ids = dict(zip(terms, ctx.find_terms(terms).tolist())) if terms else {}
+        for t in terms:
+            if ids[t] == codes.UINT32_NONE and self.args.debug_level >= 1:
+                self.log(f"Selection: term {t} is not in the dictionary; its patterns match nothing.")
+        return {"dep": resolve_patterns(dep_specs, ids), "ref": resolve_patterns(ref_specs, ids),
+                "min_support": lo, "max_support": hi}
 
     @staticmethod
     def _capture_lookup(ctx, captures):
@@ -386,12 +440,14 @@ class RDFind:
         return table.__getitem__, names.__getitem__
 
     @staticmethod
-    def _format_result(ctx, n, f, lines):
-        """The current result's n rows as text lines: written to f and/or appended to lines (neither: nothing to do)."""
+    def _format_result(ctx, n, f, lines, fmt=None):
+        """The current result's n rows as text lines: written to f and/or appended to lines (neither: nothing to do).
+        fmt: the formatter of the rows' source (default: the result; the selection view's for --select-*)."""
         if f is None and lines is None:
             return
+        fmt = ctx.format_array if fmt is None else fmt
         for off in range(0, n, FORMAT_CHUNK):
-            text = ctx.format_array(off, FORMAT_CHUNK)
+            text = fmt(off, FORMAT_CHUNK)
             if f is not None:
                 f.write(memoryview(text))
             if lines is not None:
@@ -498,6 +554,146 @@ def cind_statistics_lines(rows, top, decode, term):
         out.append(f"Most referenced: {codes.pretty_print(code, term(v1), None if v2 is None else term(v2))} "
                    f"by {cinds} CINDs")
     return out
+
+
+# ---------------------------------------------------------------------------
+# Selection patterns (--select-dep / --select-ref): pure host code
+
+_ATTR_BIT = {"s": codes.SUBJECT, "p": codes.PREDICATE, "o": codes.OBJECT}
+_SEL_INDEX = {c: i for i, c in enumerate(_lib.SEL_CODES)}
+_BINARY_MASK = sum(1 << _SEL_INDEX[c] for c in codes.BINARY_CODES)
+
+
+def _pattern_term_end(text, i):
+    """End of the term starting at text[i] inside a pattern's brackets: ntriples._term_end's rules for IRIs and
+    literals (escapes, language tags, datatypes), with ',' and ']' ending a tag, a bare datatype or a bare token where
+    N-Triples has white space."""
+    n = len(text)
+
+    def bare(j):
+        while j < n and text[j] not in ",]":
+            j += 1
+        return j
+    c = text[i]
+    if c == "<":
+        j = text.find(">", i + 1)
+        if j < 0:
+            raise ValueError(f"unterminated IRI in pattern {text!r}")
+        return j + 1
+    if c == '"':
+        j = i + 1
+        while j < n and text[j] != '"':
+            j += 2 if text[j] == "\\" else 1
+        if j >= n:
+            raise ValueError(f"unterminated literal in pattern {text!r}")
+        j += 1
+        if j < n and text[j] == "@":
+            return bare(j)
+        if j + 1 < n and text[j] == "^" and text[j + 1] == "^":
+            j += 2
+            if j < n and text[j] == "<":
+                j = text.find(">", j) + 1
+                if j <= 0:
+                    raise ValueError(f"unterminated datatype IRI in pattern {text!r}")
+                return j
+            return bare(j)
+        return j
+    return bare(i)
+
+
+def parse_capture_pattern(text):
+    """A --select-dep / --select-ref PATTERN as a list of (codes, term1, term2) alternatives, any of which a capture may
+    match: codes = the admitted capture codes as a bit set over _lib.SEL_CODES, term1 / term2 = the first / second
+    condition value as a string, None for any value.
+
+        PATTERN := TERM | PROJ '[' COND (',' COND)? ']'     PROJ := s | p | o | *     COND := ATTR '=' (TERM | '*')
+
+    The attributes are distinct, differ from PROJ and come in s < p < o order (ValueError otherwise).  s[p=T] is exactly
+    that unary capture, s[p=T,o=*] the binary captures with p=T, s[p=*] a code only, *[p=T] every capture with the
+    condition p=T (unary or binary, in either slot), a bare TERM every capture that names it as a condition value.
+    Every string codes.pretty_print produces parses to a pattern that matches exactly that capture."""
+    if not text:
+        raise ValueError("empty pattern")
+    if not (len(text) >= 2 and text[0] in "spo*" and text[1] == "["):
+        return [(_lib.SEL_ALL_CODES, text, None), (_BINARY_MASK, None, text)]
+    proj = text[0]
+    conds = []
+    i = 2
+    while True:
+        if i + 1 >= len(text) or text[i] not in _ATTR_BIT or text[i + 1] != "=":
+            raise ValueError(f"expected s=, p= or o= at offset {i} of pattern {text!r}")
+        attr = text[i]
+        i += 2
+        if i >= len(text):
+            raise ValueError(f"pattern {text!r} ends after '='")
+        j = _pattern_term_end(text, i)
+        if j == i:
+            raise ValueError(f"empty condition value in pattern {text!r}")
+        value = text[i:j]
+        conds.append((attr, None if value == "*" else value))
+        i = j
+        if i < len(text) and text[i] == "," and len(conds) < 2:
+            i += 1
+            continue
+        if i == len(text) - 1 and text[i] == "]":
+            break
+        raise ValueError(f"expected ',' or a closing ']' at offset {i} of pattern {text!r}")
+    attrs = [a for a, _ in conds]
+    if len(conds) == 2 and not _ATTR_BIT[attrs[0]] < _ATTR_BIT[attrs[1]]:
+        raise ValueError(f"the conditions of pattern {text!r} must be distinct and in s < p < o order")
+    if proj in attrs:
+        raise ValueError(f"the projection of pattern {text!r} is one of its condition attributes")
+    bits = [_ATTR_BIT[a] for a in attrs]
+    if proj != "*" or len(conds) == 2:
+        if len(conds) == 2:  # (two conditions leave one projection)
+            secondary = codes.TYPE_BIT_MASK & ~(bits[0] | bits[1])
+            if proj != "*" and _ATTR_BIT[proj] != secondary:
+                raise ValueError(f"the projection of pattern {text!r} is one of its condition attributes")
+            code = codes.create_code(bits[0], bits[1], secondary)
+            return [(1 << _SEL_INDEX[code], conds[0][1], conds[1][1])]
+        return [(1 << _SEL_INDEX[codes.create_code(bits[0], 0, _ATTR_BIT[proj])], conds[0][1], None)]
+    # *[a=T]: the unary captures with that condition, and the binary ones that hold it in the first or the second slot
+    value = conds[0][1]
+    unary = first = second = 0
+    for code in codes.ALL_CODES:
+        f1, f2, _ = codes.decode(codes.extract_primary(code))
+        if f2 == 0 and f1 == bits[0]:
+            unary |= 1 << _SEL_INDEX[code]
+        elif f2 and f1 == bits[0]:
+            first |= 1 << _SEL_INDEX[code]
+        elif f2 and f2 == bits[0]:
+            second |= 1 << _SEL_INDEX[code]
+    return [(m, a, b) for m, a, b in ((unary, value, None), (first, value, None), (second, None, value)) if m]
+
+
+def parse_support_range(text):
+    """--select-support LO[:HI] as (lo, hi); no flag: no bounds."""
+    if text is None:
+        return 0, 0xFFFFFFFF
+    lo, sep, hi = text.partition(":")
+    lo, hi = int(lo), int(hi) if sep else 0xFFFFFFFF
+    if not 0 <= lo <= hi <= 0xFFFFFFFF:
+        raise ValueError(f"--select-support {text}: expected 0 <= LO <= HI < 2^32")
+    return lo, hi
+
+
+def resolve_patterns(specs, ids):
+    """The parsed patterns of one side as (codes, value1, value2) rows for Context.select_cinds; ids: term -> id,
+    UINT32_NONE for a term the dictionary lacks (its alternatives are dropped).  A side whose patterns all miss gets one
+    pattern that admits no code, since no pattern at all would admit every capture."""
+    rows = []
+    for spec in specs:
+        for mask, t1, t2 in spec:
+            v1 = _lib.RDF_SEL_ANY if t1 is None else ids[t1]
+            v2 = _lib.RDF_SEL_ANY if t2 is None else ids[t2]
+            if (t1 is not None and v1 == codes.UINT32_NONE) or (t2 is not None and v2 == codes.UINT32_NONE):
+                continue
+            rows.append((mask, v1, v2))
+    if specs and not rows:
+        rows.append((0, _lib.RDF_SEL_ANY, _lib.RDF_SEL_ANY))
+    if len(rows) > _lib.RDF_SEL_MAX_PATTERNS:
+        raise ValueError(f"{len(rows)} selection patterns on one side; at most {_lib.RDF_SEL_MAX_PATTERNS}")
+    return rows
 
 
 def format_rows(rows, term):
