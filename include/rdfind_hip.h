@@ -607,6 +607,56 @@ rdf_status rdf_format_selected_size(rdf_ctx* ctx, uint64_t offset, uint64_t coun
 rdf_status rdf_format_selected(rdf_ctx* ctx, uint64_t offset, uint64_t count, char* out, uint64_t cap, uint64_t* bytes);
 rdf_status rdf_find_terms(rdf_ctx* ctx, const char* heap, const uint64_t* offsets, uint32_t n, uint32_t* ids);
 
+/*
+ * CIND check on the device: which of M given CINDs hold in the resident triples, and how badly the others are violated.
+ * A capture (code, value1, value2) -- the order of rdf_decode_capture; code one of 10 12 14 17 20 21 33 34 35; value2 =
+ * UINT32_MAX for a unary capture -- denotes I(c), the set of distinct values of its projection attribute over the
+ * resident triples (as rdf_copy_triples returns them) that match its condition.  Duplicate triples do not change it and
+ * a value counts wherever it appears, so o[p=a] < s[p=b] is legal.  A value may be RDF_CHK_ABSENT, a term the
+ * dictionary lacks: such a capture is empty.  Per candidate (dep, ref), in candidate order:
+ *   dep_support = |I(dep)|, ref_support = |I(ref)|, overlap = |I(dep) & I(ref)|,
+ *   n_examples  = min(n_examples asked for, dep_support - overlap) violating values, the smallest term ids of
+ *                 I(dep) \ I(ref) ascending; rdf_copy_check_examples pads each row's n_examples slots with UINT32_MAX.
+ * Classes: empty (dep_support == 0, vacuous), holding (dep_support > 0 and overlap == dep_support), violated (the rest).
+ * Duplicate candidates, dep == ref and captures shared by many candidates are allowed; no support threshold, no
+ * frequent conditions, no minimality: --use-ars, --clean-implied and the support filter play no part.
+ *
+ * One pass over s / p / o per batch (every triple probes a table of the candidates' conditions and emits capture <<
+ * joinbits | value), one radix sort of those records, run heads for the distinct values per capture, and an
+ * intersection in work items of chunk_values dependent values.  The record budget is the free HBM; candidates whose
+ * captures exceed it are checked in batches of consecutive candidates, each with its own pass over the triples.
+ *
+ * Callable at any stage once triples are resident (rdf_set_triples*, a parse, rdf_rewrite_terms, rdf_distinct_triples or
+ * any later stage); it leaves the stage, the frequent conditions, the groups, the result and any selection view exactly
+ * as they were.  The rows and examples live until the next rdf_check_cinds, new triples, rdf_rewrite_terms,
+ * rdf_distinct_triples or rdf_release_scratch; the copy calls return RDF_ERR_STATE without them.
+ * Errors: RDF_ERR_STATE without resident triples or in a sharded run's state (a rank holds a slice); RDF_ERR_ARG for a
+ * code outside the nine, a unary capture with a value2, a binary one without, an id >= the number of terms that is not
+ * RDF_CHK_ABSENT, n_examples > RDF_CHK_MAX_EXAMPLES or a null array with n > 0 (rdf_last_error names the candidate);
+ * RDF_ERR_LIMIT for n >= 2^31; RDF_ERR_OOM only when one candidate's two captures exceed the record budget
+ * (rdf_last_error names the bytes needed).  n == 0 is valid: zero rows, zeroed stats.  Single GPU.
+ */
+#define RDF_CHK_ABSENT 0xfffffffeu
+#define RDF_CHK_MAX_EXAMPLES 16u
+typedef struct { uint32_t code, value1, value2; } rdf_capture_key;
+typedef struct { rdf_capture_key dep, ref; } rdf_cind_candidate;
+typedef struct { uint32_t dep_support, ref_support, overlap, n_examples; } rdf_check_row;
+typedef struct {
+    uint64_t n_candidates, n_captures;   /* M; distinct non-empty captures among the 2M sides */
+    uint64_t n_conditions;               /* distinct conditions in the (largest batch's) condition table */
+    uint64_t n_records, n_values;        /* records emitted / distinct (capture, value), all batches */
+    uint64_t n_holding, n_violated, n_empty, n_work_items;
+    uint32_t n_batches, table_in_lds;    /* table_in_lds: every batch's table was staged in LDS */
+    uint32_t lds_slots, chunk_values;    /* the LDS table's slot cap; dependent values per work item */
+    float ms_match, ms_sort, ms_intersect, ms_total;  /* device time: count + emit passes; sort + unique; items + rows */
+} rdf_check_stats;
+rdf_status rdf_check_cinds(rdf_ctx* ctx, const rdf_cind_candidate* cands, uint64_t n, uint32_t n_examples,
+                           rdf_check_stats* stats /* may be null */);
+/* Rows [offset, offset + count) of the last check (clipped); *n_copied receives the number copied. */
+rdf_status rdf_copy_check_rows(rdf_ctx* ctx, uint64_t offset, rdf_check_row* out, uint64_t count, uint64_t* n_copied);
+/* Their example slots: n_examples (as passed to rdf_check_cinds) uint32 per row. */
+rdf_status rdf_copy_check_examples(rdf_ctx* ctx, uint64_t offset, uint32_t* out, uint64_t count, uint64_t* n_copied);
+
 /* Device time (ms) of the last call of each stage: [0] fc, [1] groups, [2] cinds. */
 rdf_status rdf_stage_times(rdf_ctx* ctx, float* ms3);
 /* Device time (ms) of each kernel family (RDF_T_*) in the last calls; count <= RDF_NUM_TIMERS. */

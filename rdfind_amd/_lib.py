@@ -39,8 +39,11 @@ EXPORTED_SYMBOLS = (
     "rdf_rewrite_terms", "rdf_condition_histogram", "rdf_join_histogram", "rdf_copy_histogram", "rdf_count_literals",
     "rdf_cind_stats_begin", "rdf_cind_stats_add", "rdf_cind_stats_end", "rdf_cind_histogram", "rdf_copy_top_refs",
     "rdf_select_cinds", "rdf_selected_count", "rdf_copy_selected_decoded", "rdf_format_selected_size",
-    "rdf_format_selected", "rdf_find_terms",
+    "rdf_format_selected", "rdf_find_terms", "rdf_check_cinds", "rdf_copy_check_rows", "rdf_copy_check_examples",
 )
+# CIND check (rdf_check_cinds): a term the dictionary lacks, the most examples per candidate
+RDF_CHK_ABSENT = 0xFFFFFFFE
+RDF_CHK_MAX_EXAMPLES = 16
 # result selection (rdf_select_cinds): wildcard value, patterns per side, flags; the code index of a pattern's `codes`
 # bits numbers the capture codes in ascending order
 RDF_SEL_ANY = 0xFFFFFFFF
@@ -188,6 +191,17 @@ class CindQuery(ctypes.Structure):
                 ("min_support", ctypes.c_uint32), ("max_support", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
+class CheckStats(ctypes.Structure):
+    """rdf_check_stats (include/rdfind_hip.h)."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("n_candidates", "n_captures", "n_conditions", "n_records", "n_values",
+                                               "n_holding", "n_violated", "n_empty", "n_work_items")] + \
+               [(n, ctypes.c_uint32) for n in ("n_batches", "table_in_lds", "lds_slots", "chunk_values")] + \
+               [(n, ctypes.c_float) for n in ("ms_match", "ms_sort", "ms_intersect", "ms_total")]
+
+
+# rdf_check_row
+CHECK_DTYPE = np.dtype([("dep_support", "<u4"), ("ref_support", "<u4"), ("overlap", "<u4"), ("n_examples", "<u4")])
+
 _lib = None
 
 
@@ -245,6 +259,9 @@ def load():
         "rdf_format_selected_size": (i32, [P, u64, u64, ctypes.POINTER(u64)]),
         "rdf_format_selected": (i32, [P, u64, u64, P, u64, ctypes.POINTER(u64)]),
         "rdf_find_terms": (i32, [P, ctypes.c_char_p, P, u32, P]),
+        "rdf_check_cinds": (i32, [P, P, u64, u32, ctypes.POINTER(CheckStats)]),
+        "rdf_copy_check_rows": (i32, [P, u64, P, u64, ctypes.POINTER(u64)]),
+        "rdf_copy_check_examples": (i32, [P, u64, P, u64, ctypes.POINTER(u64)]),
         "rdf_frequent_conditions": (i32, [P, u32, ctypes.POINTER(FcStats)]),
         "rdf_build_capture_groups": (i32, [P, ctypes.c_char_p, ctypes.POINTER(GroupStats)]),
         "rdf_discover_cinds": (i32, [P, u32, ctypes.POINTER(CindStats)]),
@@ -664,6 +681,33 @@ class Context:
     def format_selected(self, offset=0, count=None) -> bytes:
         """As format_selected_array, as bytes."""
         return self.format_selected_array(offset, count).tobytes()
+
+    # -- CIND check ---------------------------------------------------------------------------
+    def check_cinds(self, cands, examples: int = 0):
+        """rdf_check_cinds: `cands` is an (M, 6) uint32 array [dep_code, d1, d2, ref_code, r1, r2] (value2 = 0xFFFFFFFF
+        for a unary capture, RDF_CHK_ABSENT for a term the dictionary lacks).  Returns the rows (CHECK_DTYPE) and the
+        (M, examples) violating term ids, ascending and padded with 0xFFFFFFFF; ``last_check`` holds the stats."""
+        cands = np.ascontiguousarray(cands, dtype=np.uint32).reshape(-1, 6)
+        m = cands.shape[0]
+        st = CheckStats()
+        self._check(self.lib.rdf_check_cinds(self.ptr, cands.ctypes.data if m else None, m, int(examples), ctypes.byref(st)),
+                    "rdf_check_cinds")
+        self.last_check = _struct_dict(st)
+        return self.check_rows(0, m), self.check_examples(0, m, int(examples))
+
+    def check_rows(self, offset: int, count: int) -> np.ndarray:
+        rows = np.empty(count, dtype=CHECK_DTYPE)
+        got = ctypes.c_uint64()
+        self._check(self.lib.rdf_copy_check_rows(self.ptr, offset, rows.ctypes.data, count, ctypes.byref(got)),
+                    "rdf_copy_check_rows")
+        return rows[: got.value]
+
+    def check_examples(self, offset: int, count: int, examples: int) -> np.ndarray:
+        ex = np.empty((count, examples), dtype=np.uint32)
+        got = ctypes.c_uint64()
+        self._check(self.lib.rdf_copy_check_examples(self.ptr, offset, ex.ctypes.data, count, ctypes.byref(got)),
+                    "rdf_copy_check_examples")
+        return ex[: got.value]
 
     def cind_stats_times(self):
         """(explicit, class, end) device ms of the last result statistics (rdf_test_cind_stats_times)."""

@@ -4314,6 +4314,7 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_nt_assign_chunk(const u32* __rest
 #include "histo.inl"
 #include "cindstats.inl"
 #include "select.inl"
+#include "check.inl"
 
 }  // namespace rdf
 

@@ -74,6 +74,16 @@ using namespace rdf;
     B(RUN, slwoff) B(RUN, slrcnt) B(RUN, slroff) B(RUN, slkpos) B(RUN, sltcnt) B(RUN, sltoff) B(RUN, sllcnt) B(RUN, slloff) \
     B(RUN, sllist) B(RUN, slmc) B(RUN, slmrank) B(RUN, slmoff) B(RUN, slmflag) B(RUN, slmkpos) B(RUN, slq) B(RUN, slqoff) \
     B(RUN, slids) \
+    /* CIND check (check.inl).  The result: chk_rows, chk_ex.  Per call: the candidates, their 2M capture keys and the */ \
+    /* sort scratch, head flags and their scan, the Q distinct captures, each side's capture index, per capture its */ \
+    /* matching triples and whether the batch needs it, the condition table, per candidate its record bound and the */ \
+    /* scanned bounds.  Per batch: the records and their sort scratch, head flags, their scan, the distinct values, */ \
+    /* the captures' value offsets, per candidate its work items and their scan, per item its violations and their */ \
+    /* scan; the error word, record cursor, overflow flag and class counters */ \
+    B(RUN, chk_rows) B(RUN, chk_ex) B(RUN, chk_cand) B(RUN, chk_keys) B(RUN, chk_keys_tmp) B(RUN, chk_flag) B(RUN, chk_pos) \
+    B(RUN, chk_ucap) B(RUN, chk_side) B(RUN, chk_cnt) B(RUN, chk_inb) B(RUN, chk_tab) B(RUN, chk_w) B(RUN, chk_woff) \
+    B(RUN, chk_rec) B(RUN, chk_rec_tmp) B(RUN, chk_qval) B(RUN, chk_qoff) B(RUN, chk_nit) B(RUN, chk_ioff) \
+    B(RUN, chk_viol) B(RUN, chk_vpre) B(RUN, chk_scal) \
     /* frequent conditions */ \
     B(RUN, frank) B(RUN, fval) B(RUN, fext) \
     B(RUN, cnt) B(SPARE_FC, tkeys) B(RUN, tcnt) B(RUN, bkeys) B(RUN, bkeys_tmp) B(RUN, lkeys) B(RUN, lvals) B(RUN, flags) \
@@ -212,6 +222,12 @@ struct rdf_ctx : CtxBuffers {
     // sel_rows rows in sel_runs runs; dropped wherever the result it names goes (the resets above, and rdf_next_page)
     bool sel_valid = false;
     u64 sel_rows = 0, sel_runs = 0;
+    // CIND check (check.inl): chk_rows / chk_ex hold the chk_M rows of the last rdf_check_cinds and chk_nex example
+    // slots per row; dropped wherever the resident triples change, and by rdf_release_scratch
+    bool chk_valid = false;
+    u64 chk_M = 0;
+    u32 chk_nex = 0;
+    hipEvent_t chk_ev[5] = {};
     u32 parse_flags = 0;
     u64 pc_n = 0, pc_V = 0, pc_lines = 0, pc_chunks = 0, pc_heap = 0, pc_slots = 0, pc_growths = 0;
     float pc_ms = 0;
@@ -647,6 +663,7 @@ rdf_status rdf_ctx_create(int device, rdf_ctx** out) {
     if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&c->hread_d, c->hread, 0);
     for (int i = 0; i < 8 && e == hipSuccess; ++i) e = hipEventCreate(&c->ev[i]);
     for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&c->cs_ev[i]);
+    for (int i = 0; i < 5 && e == hipSuccess; ++i) e = hipEventCreate(&c->chk_ev[i]);
     for (int i = 0; i < 2 * RDF_NUM_TIMERS * rdf_ctx::kTSeg && e == hipSuccess; ++i) e = hipEventCreate(&c->tev[i]);
     if (e != hipSuccess) {
         rdf_ctx_destroy(c);
@@ -669,6 +686,8 @@ void rdf_ctx_destroy(rdf_ctx* c) {
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : c->cs_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto& e : c->chk_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : c->tev)
         if (e) (void)hipEventDestroy(e);
@@ -710,7 +729,7 @@ static void release_run_buffers(rdf_ctx* c, u64 n_next, bool always = false) {
     const u64 held = held_bytes(c) - class_bytes(c, BUF_INPUT);
     if (!always && held <= std::max<u64>(4ull << 30, n_next << 10)) return;
     (void)hipStreamSynchronize(c->stream);
-    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = c->chk_valid = false;
     for_each_buf(c, [](DevBuf& b, const BufEntry& e) {
         if (e.cls != BUF_INPUT) b.release();
     });
@@ -777,7 +796,7 @@ rdf_status rdf_set_triples(rdf_ctx* c, const uint32_t* s, const uint32_t* p, con
     c->n = n;
     c->V = num_terms;
     c->stage = 1;
-    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;  // a paged run's state belongs to the previous input
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = c->chk_valid = false;  // a paged run's state belongs to the previous input
     c->parsed_dict = false;
     c->ingest_sharded = false;
     return RDF_OK;
@@ -796,7 +815,7 @@ rdf_status rdf_set_triples_device(rdf_ctx* c, const uint32_t* s, const uint32_t*
     c->n = n;
     c->V = num_terms;
     c->stage = 1;
-    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;  // a paged run's state belongs to the previous input
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = c->chk_valid = false;  // a paged run's state belongs to the previous input
     c->parsed_dict = false;
     c->ingest_sharded = false;
     return RDF_OK;
@@ -848,7 +867,7 @@ rdf_status rdf_distinct_triples(rdf_ctx* c, uint64_t* n_distinct, float* ms) {
     if (ms) HIP_TRY(c, hipEventElapsedTime(ms, c->ev[6], c->ev[7]));
     c->n = kept;
     c->stage = 1;
-    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;  // a paged run's state belongs to the previous input
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = c->chk_valid = false;  // a paged run's state belongs to the previous input
     if (n_distinct) *n_distinct = kept;
     return RDF_OK;
 }
@@ -960,7 +979,7 @@ rdf_status rdf_parse_ntriples(rdf_ctx* c, const char* text, uint64_t nbytes, uin
     c->n = n;
     c->V = (u32)V;
     c->stage = 1;
-    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;  // a paged run's state belongs to the previous input
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = c->chk_valid = false;  // a paged run's state belongs to the previous input
     c->n_terms_parsed = V;
     c->parsed_dict = true;
     c->ingest_sharded = false;
@@ -1037,7 +1056,7 @@ rdf_status rdf_parse_begin(rdf_ctx* c, uint32_t flags, uint64_t reserve_triples)
     c->ntext.release();
     c->ntheap.release();
     c->stage = 0;
-    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = c->chk_valid = false;
     c->parsed_dict = false;
     c->dict_in_heap = false;
     c->ingest_sharded = false;
@@ -1229,7 +1248,7 @@ rdf_status rdf_parse_end(rdf_ctx* c, rdf_parse_stats* stats) {
     c->n = c->pc_n;
     c->V = (u32)c->pc_V;
     c->stage = 1;
-    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = c->chk_valid = false;
     c->n_terms_parsed = c->pc_V;
     c->parsed_dict = true;
     c->dict_in_heap = true;
@@ -1465,7 +1484,7 @@ rdf_status rdf_rewrite_terms(rdf_ctx* c, uint32_t flags, const char* key_heap, c
     c->p = c->tp.as<u32>();
     c->o = c->to.as<u32>();
     c->stage = 1;
-    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = c->chk_valid = false;
     return RDF_OK;
 }
 
@@ -5272,7 +5291,7 @@ static rdf_status sh_phase24(rdf_ctx* c, rdf_exchange* req) {
     c->parsed_dict = false;
     c->ingest_sharded = true;
     c->stage = 1;
-    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;  // a paged run's state belongs to the previous input
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = c->chk_valid = false;  // a paged run's state belongs to the previous input
     memset(req, 0, sizeof(*req));
     req->op = RDF_X_DONE;
     c->sh_phase = 9;
@@ -5398,7 +5417,7 @@ rdf_status rdf_shard_parse_begin(rdf_ctx* c, uint32_t rank, uint32_t nranks, con
     c->sh_phase = 20;
     c->x_imported = true;
     c->stage = 0;  // no usable triples until the global ids arrive
-    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;
+    c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = c->chk_valid = false;
     if (n_triples) *n_triples = n;
     return RDF_OK;
 }
@@ -6700,6 +6719,329 @@ rdf_status rdf_find_terms(rdf_ctx* c, const char* heap, const uint64_t* offsets,
     return ctx_copy(c, ids, c->slids.p, (u64)n * 4, hipMemcpyDeviceToHost) == hipSuccess
                ? RDF_OK
                : fail(c, RDF_ERR_HIP, "rdf_find_terms: copying the ids");
+}
+
+// ------------------------------------------------------------------------------------------------
+// CIND check (check.inl): rdf_check_cinds and its copy calls.  Buffers (chk_*) and timing events of their own, the
+// workspace of the sort and scan primitives: no pipeline state changes.
+
+// bytes one record of a batch takes: the record and its sort scratch (16), head flag, scanned flag, distinct value (12),
+// and room for the primitives' workspace
+static constexpr u64 CHK_REC_BYTES = 32;
+// chk_scal: u64 words [0] first invalid candidate << 3 | reason, [1] record cursor, [2..4] holding / violated / empty,
+// [5] overflow flag (u32), [6] conditions in the table (u32)
+enum { CHK_S_ERR = 0, CHK_S_CURSOR, CHK_S_CLS, CHK_S_OVER = 5, CHK_S_NCOND = 6, CHK_S_WORDS = 8 };
+
+struct ChkTable {
+    u32 slots = 0, conds = 0;
+    bool lds = false;
+};
+
+// the condition table of the captures with inb[q] (null: all Q) in chk_tab, sized a power of two >= 4 x its conditions
+static rdf_status chk_table(rdf_ctx* c, const unsigned char* inb, u64 Q, u32 lds_slots, ChkTable* t) {
+    hipStream_t st = c->stream;
+    u64* scal = c->chk_scal.as<u64>();
+    u64 T = next_pow2(4 * std::max<u64>(Q, 1));
+    if (T > (1ull << 31)) return fail(c, RDF_ERR_LIMIT, "rdf_check_cinds: too many distinct captures for one condition table");
+    for (int round = 0; round < 2; ++round) {  // once by the captures' number, again once the conditions are counted
+        ENSURE(c, chk_tab, T * sizeof(ulonglong2));
+        HIP_TRY(c, hipMemsetAsync(c->chk_tab.p, 0xff, T * sizeof(ulonglong2), st));
+        HIP_TRY(c, hipMemsetAsync(scal + CHK_S_NCOND, 0, 8, st));
+        hipLaunchKernelGGL(k_chk_table, dim3(grid_for(Q, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->chk_ucap.as<u64>(), Q, inb,
+                           c->chk_tab.as<ulonglong2>(), (u32)(T - 1), (u32*)(scal + CHK_S_NCOND));
+        HIP_TRY(c, hipGetLastError());
+        TRY(read_u32(c, scal + CHK_S_NCOND, &t->conds));
+        const u64 want = next_pow2(4 * std::max<u64>(t->conds, 1));
+        if (want == T) break;
+        T = want;
+    }
+    t->slots = (u32)T;
+    t->lds = T <= lds_slots;
+    return RDF_OK;
+}
+
+// one pass of k_chk_match over the resident triples: the count form (cnt) or the write form (records to out[0, cap))
+static rdf_status chk_match(rdf_ctx* c, const ChkTable& t, bool write, int joinbits, u64* out, u64 cap) {
+    hipStream_t st = c->stream;
+    if (!c->n) return RDF_OK;
+    u64* scal = c->chk_scal.as<u64>();
+    const dim3 g(grid_for(c->n, RDF_BLOCK * CHK_TRIPLES, kGrid)), blk(RDF_BLOCK);
+    const size_t lds = t.lds ? (size_t)t.slots * (sizeof(ulonglong2) + (write ? 0 : 8)) : write ? 0 : (size_t)CHK_PRIV * 8;
+#define RDF_CHK_MATCH(LDS, WRITE)                                                                                       \
+    hipLaunchKernelGGL((k_chk_match<LDS, WRITE>), g, blk, lds, st, c->s, c->p, c->o, c->n, c->chk_tab.as<ulonglong2>(), \
+                       t.slots - 1, joinbits, c->chk_cnt.as<u32>(), scal + CHK_S_CURSOR, out, cap, (u32*)(scal + CHK_S_OVER))
+    if (t.lds && write) RDF_CHK_MATCH(true, true);
+    else if (t.lds) RDF_CHK_MATCH(true, false);
+    else if (write) RDF_CHK_MATCH(false, true);
+    else RDF_CHK_MATCH(false, false);
+#undef RDF_CHK_MATCH
+    HIP_TRY(c, hipGetLastError());
+    return RDF_OK;
+}
+
+// device time between two of the check's events, added to *ms (after a stream wait)
+static rdf_status chk_add_time(rdf_ctx* c, int a, int b, float* ms) {
+    float t = 0;
+    HIP_TRY(c, hipEventElapsedTime(&t, c->chk_ev[a], c->chk_ev[b]));
+    *ms += t;
+    return RDF_OK;
+}
+
+// candidates [c0, c1): their captures' records (R of them, through table t), distinct values, work items and rows
+static rdf_status chk_batch(rdf_ctx* c, u64 c0, u64 c1, u64 Q, u64 R, const ChkTable& t, int joinbits, u32 nex,
+                            rdf_check_stats* S) {
+    hipStream_t st = c->stream;
+    u64* scal = c->chk_scal.as<u64>();
+    const u32* side = c->chk_side.as<u32>();
+    const dim3 blk(RDF_BLOCK);
+    ENSURE(c, chk_qoff, (Q + 1) * 4);
+    u64 D = 0;
+    HIP_TRY(c, hipEventRecord(c->chk_ev[1], st));
+    if (R) {
+        ENSURE(c, chk_rec, R * 8);
+        ENSURE(c, chk_rec_tmp, R * 8);
+        ENSURE(c, chk_flag, R * 4);
+        ENSURE(c, chk_pos, (R + 1) * 4);
+        HIP_TRY(c, hipMemsetAsync(scal + CHK_S_CURSOR, 0, 8, st));
+        TRY(chk_match(c, t, true, joinbits, c->chk_rec.as<u64>(), R));
+        u64 got[2] = {0, 0};
+        TRY(read_multi(c, {{scal + CHK_S_CURSOR, 8}, {scal + CHK_S_OVER, 4}}, got));
+        if (got[0] != R || got[1])
+            return fail(c, RDF_ERR_HIP, "rdf_check_cinds: the emission wrote " + std::to_string(got[0]) + " records, the count pass " +
+                                            std::to_string(R));
+        HIP_TRY(c, hipEventRecord(c->chk_ev[2], st));
+        u64 *k = c->chk_rec.as<u64>(), *tmp = c->chk_rec_tmp.as<u64>();
+        HIP_TRY(c, radix_sort_u64(c->ws, k, tmp, R, bits_for(Q - 1) + joinbits, st));
+        const dim3 g(grid_for(R, RDF_BLOCK, kGrid));
+        hipLaunchKernelGGL(k_histo_heads, g, blk, 0, st, k, R, 0, c->chk_flag.as<u32>());
+        HIP_TRY(c, exclusive_scan_u32(c->ws, c->chk_flag.as<u32>(), c->chk_pos.as<u32>(), R, c->chk_pos.as<u32>() + R, st));
+        u32 d32 = 0;
+        TRY(read_u32(c, c->chk_pos.as<u32>() + R, &d32));
+        D = d32;
+        ENSURE(c, chk_qval, std::max<u64>(D, 1) * 4);
+        hipLaunchKernelGGL(k_chk_values, g, blk, 0, st, k, R, c->chk_flag.as<u32>(), c->chk_pos.as<u32>(), (1ull << joinbits) - 1,
+                           c->chk_qval.as<u32>());
+        hipLaunchKernelGGL(k_chk_qoff, dim3(grid_for(Q + 1, RDF_BLOCK, kGrid)), blk, 0, st, k, R, c->chk_pos.as<u32>(), Q, joinbits,
+                           c->chk_qoff.as<u32>());
+        HIP_TRY(c, hipGetLastError());
+    } else {
+        HIP_TRY(c, hipEventRecord(c->chk_ev[2], st));
+        ENSURE(c, chk_qval, 4);
+        HIP_TRY(c, hipMemsetAsync(c->chk_qoff.p, 0, (Q + 1) * 4, st));
+    }
+    HIP_TRY(c, hipEventRecord(c->chk_ev[3], st));
+    // work items: (candidate, chunk of the dependent's values)
+    const u64 Mb = c1 - c0;
+    u64 W = 0;
+    ENSURE(c, chk_nit, Mb * 4);
+    ENSURE(c, chk_ioff, (Mb + 1) * 8);
+    const dim3 gm(grid_for(Mb, RDF_BLOCK, kGrid));
+    hipLaunchKernelGGL(k_chk_items, gm, blk, 0, st, side, c0, c1, c->chk_qoff.as<u32>(), c->chk_nit.as<u32>());
+    HIP_TRY(c, hipGetLastError());
+    TRY(sel_scan(c, c->chk_nit.as<u32>(), c->chk_ioff.as<u64>(), Mb, &W));
+    ENSURE(c, chk_viol, std::max<u64>(W, 1) * 4);
+    ENSURE(c, chk_vpre, (W + 1) * 8);
+    if (W) {
+        const dim3 gw(vgrid(W));
+        hipLaunchKernelGGL(k_chk_intersect<false>, gw, blk, 0, st, c->chk_ioff.as<u64>(), Mb, W, c0, side, c->chk_qoff.as<u32>(),
+                           c->chk_qval.as<u32>(), c->chk_viol.as<u32>(), (const u64*)nullptr, 0u, (u32*)nullptr);
+        HIP_TRY(c, exclusive_scan_u32_u64(c->ws, c->chk_viol.as<u32>(), c->chk_vpre.as<u64>(), W, c->chk_vpre.as<u64>() + W, st));
+        if (nex)
+            hipLaunchKernelGGL(k_chk_intersect<true>, gw, blk, 0, st, c->chk_ioff.as<u64>(), Mb, W, c0, side,
+                               c->chk_qoff.as<u32>(), c->chk_qval.as<u32>(), c->chk_viol.as<u32>(), c->chk_vpre.as<u64>(), nex,
+                               c->chk_ex.as<u32>());
+    } else {
+        HIP_TRY(c, hipMemsetAsync(c->chk_vpre.p, 0, 8, st));
+    }
+    hipLaunchKernelGGL(k_chk_rows, gm, blk, 0, st, c0, Mb, side, c->chk_qoff.as<u32>(), c->chk_ioff.as<u64>(),
+                       c->chk_vpre.as<u64>(), nex, c->chk_rows.as<rdf_check_row>());
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->chk_ev[4], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    TRY(chk_add_time(c, 1, 2, &S->ms_match));
+    TRY(chk_add_time(c, 2, 3, &S->ms_sort));
+    TRY(chk_add_time(c, 3, 4, &S->ms_intersect));
+    S->n_records += R;
+    S->n_values += D;
+    S->n_work_items += W;
+    S->n_batches += 1;
+    S->n_conditions = std::max<u64>(S->n_conditions, t.conds);
+    S->table_in_lds = S->table_in_lds && t.lds ? 1u : 0u;
+    return RDF_OK;
+}
+
+static rdf_status chk_body(rdf_ctx* c, const rdf_cind_candidate* cands, u64 M, u32 nex, rdf_check_stats* S) {
+    hipStream_t st = c->stream;
+    const dim3 blk(RDF_BLOCK);
+    const u32 V = c->V;
+    const int joinbits = bits_for(V ? V - 1 : 0);
+    ENSURE(c, chk_scal, CHK_S_WORDS * 8);
+    ENSURE(c, chk_cand, M * sizeof(rdf_cind_candidate));
+    ENSURE(c, chk_keys, 2 * M * 8);
+    ENSURE(c, chk_keys_tmp, 2 * M * 8);
+    ENSURE(c, chk_flag, 2 * M * 4);
+    ENSURE(c, chk_pos, (2 * M + 1) * 4);
+    ENSURE(c, chk_side, 2 * M * 4);
+    ENSURE(c, chk_rows, M * sizeof(rdf_check_row));
+    ENSURE(c, chk_ex, std::max<u64>(M * nex, 1) * 4);
+    u64* scal = c->chk_scal.as<u64>();
+    HIP_TRY(c, hipEventRecord(c->chk_ev[0], st));
+    HIP_TRY(c, hipMemcpyAsync(c->chk_cand.p, cands, M * sizeof(rdf_cind_candidate), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(scal, 0, CHK_S_WORDS * 8, st));
+    HIP_TRY(c, hipMemsetAsync(scal + CHK_S_ERR, 0xff, 8, st));
+    HIP_TRY(c, hipMemsetAsync(c->chk_ex.p, 0xff, std::max<u64>(M * nex, 1) * 4, st));
+    const rdf_cind_candidate* dc = c->chk_cand.as<rdf_cind_candidate>();
+    const dim3 gm(grid_for(M, RDF_BLOCK, kGrid)), g2(grid_for(2 * M, RDF_BLOCK, kGrid));
+    // the distinct captures and each side's index among them
+    hipLaunchKernelGGL(k_chk_keys, gm, blk, 0, st, dc, M, V, c->chk_keys.as<u64>(), scal + CHK_S_ERR);
+    HIP_TRY(c, hipGetLastError());
+    u64 err = 0;
+    TRY(read_u64(c, scal + CHK_S_ERR, &err));
+    if (err != EMPTY64) {
+        static const char* const why[] = {"", "a capture code outside 10 12 14 17 20 21 33 34 35", "a unary capture with a value2",
+                                          "a binary capture without a value2",
+                                          "a term id >= the number of terms that is not RDF_CHK_ABSENT"};
+        return fail(c, RDF_ERR_ARG, "rdf_check_cinds: candidate " + std::to_string(err >> 3) + " has " + why[err & 7]);
+    }
+    u64 *k = c->chk_keys.as<u64>(), *tmp = c->chk_keys_tmp.as<u64>();
+    HIP_TRY(c, radix_sort_u64(c->ws, k, tmp, 2 * M, 64, st));
+    hipLaunchKernelGGL(k_chk_cap_heads, g2, blk, 0, st, k, 2 * M, c->chk_flag.as<u32>());
+    HIP_TRY(c, exclusive_scan_u32(c->ws, c->chk_flag.as<u32>(), c->chk_pos.as<u32>(), 2 * M, c->chk_pos.as<u32>() + 2 * M, st));
+    u32 q32 = 0;
+    TRY(read_u32(c, c->chk_pos.as<u32>() + 2 * M, &q32));
+    const u64 Q = q32;
+    S->n_candidates = M;
+    S->n_captures = Q;
+    S->chunk_values = CHK_CHUNK;
+    u32 lds_slots = CHK_LDS_SLOTS;
+    if (c->sw.check_lds_slots.set) {
+        lds_slots = (u32)std::min<u64>(c->sw.check_lds_slots.v, CHK_LDS_SLOTS);
+        while (lds_slots & (lds_slots - 1)) lds_slots &= lds_slots - 1;  // (a power of two, or 0: never in LDS)
+    }
+    S->lds_slots = lds_slots;
+    if (!Q) {  // every side is empty: no capture to look for
+        HIP_TRY(c, hipMemsetAsync(c->chk_rows.p, 0, M * sizeof(rdf_check_row), st));
+        HIP_TRY(c, hipEventRecord(c->chk_ev[1], st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        S->n_empty = M;
+        return chk_add_time(c, 0, 1, &S->ms_total);
+    }
+    ENSURE(c, chk_ucap, Q * 8);
+    hipLaunchKernelGGL(k_chk_cap_compact, g2, blk, 0, st, k, 2 * M, c->chk_flag.as<u32>(), c->chk_pos.as<u32>(),
+                       c->chk_ucap.as<u64>());
+    hipLaunchKernelGGL(k_chk_sides, g2, blk, 0, st, dc, M, V, c->chk_ucap.as<u64>(), Q, c->chk_side.as<u32>());
+    HIP_TRY(c, hipGetLastError());
+    // count pass: matching triples per capture, through the table of all captures
+    const u64 QM = std::max(Q, M);
+    ENSURE(c, chk_cnt, Q * 4);
+    ENSURE(c, chk_inb, Q);
+    ENSURE(c, chk_w, QM * 4);
+    ENSURE(c, chk_woff, (QM + 1) * 8);
+    HIP_TRY(c, hipMemsetAsync(c->chk_cnt.p, 0, Q * 4, st));
+    ChkTable all;
+    TRY(chk_table(c, nullptr, Q, lds_slots, &all));
+    HIP_TRY(c, hipEventRecord(c->chk_ev[1], st));
+    TRY(chk_match(c, all, false, joinbits, nullptr, 0));
+    HIP_TRY(c, hipEventRecord(c->chk_ev[2], st));
+    const dim3 gq(grid_for(Q, RDF_BLOCK, kGrid));
+    hipLaunchKernelGGL(k_chk_masked, gq, blk, 0, st, c->chk_cnt.as<u32>(), (const unsigned char*)nullptr, Q, c->chk_w.as<u32>());
+    HIP_TRY(c, hipGetLastError());
+    u64 total = 0;
+    TRY(sel_scan(c, c->chk_w.as<u32>(), c->chk_woff.as<u64>(), Q, &total));
+    TRY(chk_add_time(c, 1, 2, &S->ms_match));
+    // the record budget: what the free HBM (and the check's own record buffers) holds
+    u64 budget = 0;
+    if (c->sw.check_records.set) {
+        budget = c->sw.check_records.v;
+    } else {
+        size_t fr = 0, tot = 0;
+        HIP_TRY(c, hipMemGetInfo(&fr, &tot));
+        budget = (fr + c->chk_rec.cap + c->chk_rec_tmp.cap + c->chk_qval.cap) / CHK_REC_BYTES;
+    }
+    budget = std::min<u64>(budget, (1ull << 32) - 2);  // (one sort)
+    S->table_in_lds = 1;
+    if (total <= budget) {
+        TRY(chk_batch(c, 0, M, Q, total, all, joinbits, nex, S));
+    } else {
+        // batches of consecutive candidates, closed where the sum of the candidates' own needs would pass the budget
+        hipLaunchKernelGGL(k_chk_weights, gm, blk, 0, st, c->chk_side.as<u32>(), M, c->chk_cnt.as<u32>(), c->chk_w.as<u32>());
+        HIP_TRY(c, hipGetLastError());
+        u64 wsum = 0;
+        TRY(sel_scan(c, c->chk_w.as<u32>(), c->chk_woff.as<u64>(), M, &wsum));
+        std::vector<u64> hw(M + 1);
+        HIP_TRY(c, ctx_copy(c, hw.data(), c->chk_woff.p, (M + 1) * 8, hipMemcpyDeviceToHost));
+        for (u64 c0 = 0; c0 < M;) {
+            const u64 need = hw[c0 + 1] - hw[c0];
+            if (need > budget)
+                return fail(c, RDF_ERR_OOM, "rdf_check_cinds: candidate " + std::to_string(c0) + " alone needs " + std::to_string(need) +
+                                                " records (" + std::to_string(need * CHK_REC_BYTES) + " bytes), the record budget is " +
+                                                std::to_string(budget) + " (" + std::to_string(budget * CHK_REC_BYTES) + " bytes)");
+            const u64 c1 = (u64)(std::upper_bound(hw.begin() + c0, hw.end(), hw[c0] + budget) - hw.begin()) - 1;
+            unsigned char* inb = c->chk_inb.as<unsigned char>();
+            HIP_TRY(c, hipMemsetAsync(inb, 0, Q, st));
+            hipLaunchKernelGGL(k_chk_mark, dim3(grid_for(2 * (c1 - c0), RDF_BLOCK, kGrid)), blk, 0, st, c->chk_side.as<u32>(), c0, c1,
+                               inb);
+            hipLaunchKernelGGL(k_chk_masked, gq, blk, 0, st, c->chk_cnt.as<u32>(), inb, Q, c->chk_w.as<u32>());
+            HIP_TRY(c, hipGetLastError());
+            u64 R = 0;
+            TRY(sel_scan(c, c->chk_w.as<u32>(), c->chk_woff.as<u64>(), Q, &R));
+            ChkTable t;
+            TRY(chk_table(c, inb, Q, lds_slots, &t));
+            TRY(chk_batch(c, c0, c1, Q, R, t, joinbits, nex, S));
+            c0 = c1;
+        }
+    }
+    hipLaunchKernelGGL(k_chk_classes, gm, blk, 0, st, c->chk_rows.as<rdf_check_row>(), M, scal + CHK_S_CLS);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->chk_ev[1], st));
+    u64 cls[3] = {0, 0, 0};
+    TRY(read_multi(c, {{scal + CHK_S_CLS, 8}, {scal + CHK_S_CLS + 1, 8}, {scal + CHK_S_CLS + 2, 8}}, cls));
+    S->n_holding = cls[0];
+    S->n_violated = cls[1];
+    S->n_empty = cls[2];
+    return chk_add_time(c, 0, 1, &S->ms_total);
+}
+
+rdf_status rdf_check_cinds(rdf_ctx* c, const rdf_cind_candidate* cands, uint64_t n, uint32_t n_examples, rdf_check_stats* stats) {
+    if (!c) return RDF_ERR_ARG;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if ((c->sh_phase >= 0 && c->sh_phase != 9) || (c->nranks > 1 && c->stage >= 3) || c->ingest_sharded)
+        return fail(c, RDF_ERR_STATE, "rdf_check_cinds reads one GPU's triples, not a sharded run's (a rank holds a slice)");
+    if (c->stage < 1) return fail(c, RDF_ERR_STATE, "rdf_set_triples must be called first");
+    if (n && !cands) return fail(c, RDF_ERR_ARG, "candidates counted but not given");
+    if (n_examples > RDF_CHK_MAX_EXAMPLES)
+        return fail(c, RDF_ERR_ARG, "at most " + std::to_string(RDF_CHK_MAX_EXAMPLES) + " examples per candidate");
+    if (n >= (1ull << 31)) return fail(c, RDF_ERR_LIMIT, "rdf_check_cinds: n must be < 2^31 candidates");
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->chk_valid = false;
+    rdf_check_stats S = {};
+    if (n) TRY(chk_body(c, cands, n, n_examples, &S));
+    c->chk_M = n;
+    c->chk_nex = n_examples;
+    c->chk_valid = true;
+    if (stats) *stats = S;
+    return RDF_OK;
+}
+
+rdf_status rdf_copy_check_rows(rdf_ctx* c, uint64_t offset, rdf_check_row* out, uint64_t count, uint64_t* n_copied) {
+    if (!c || (count && !out)) return RDF_ERR_ARG;
+    if (!c->chk_valid) return fail(c, RDF_ERR_STATE, "rdf_copy_check_rows: no check result (rdf_check_cinds comes first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const u64 m = offset >= c->chk_M ? 0 : std::min<u64>(count, c->chk_M - offset);
+    if (m) HIP_TRY(c, ctx_copy(c, out, c->chk_rows.as<rdf_check_row>() + offset, m * sizeof(rdf_check_row), hipMemcpyDeviceToHost));
+    if (n_copied) *n_copied = m;
+    return RDF_OK;
+}
+
+rdf_status rdf_copy_check_examples(rdf_ctx* c, uint64_t offset, uint32_t* out, uint64_t count, uint64_t* n_copied) {
+    if (!c || (count && !out)) return RDF_ERR_ARG;
+    if (!c->chk_valid) return fail(c, RDF_ERR_STATE, "rdf_copy_check_examples: no check result (rdf_check_cinds comes first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const u64 m = offset >= c->chk_M ? 0 : std::min<u64>(count, c->chk_M - offset);
+    if (m && c->chk_nex)
+        HIP_TRY(c, ctx_copy(c, out, c->chk_ex.as<u32>() + offset * c->chk_nex, m * c->chk_nex * 4, hipMemcpyDeviceToHost));
+    if (n_copied) *n_copied = m;
+    return RDF_OK;
 }
 
 rdf_status rdf_kernel_times(rdf_ctx* c, float* ms, int count) {

@@ -109,6 +109,11 @@ static inline RankPhase rank_phase(const char* v) {  // "rank:phase"; anything e
        "pivot-holder election on log-size buckets (holder_key; 0: exact sizes; at most 8)") \
     SW(hot_balance, bool, true, "RDFIND_HOT_BALANCE", atoi(v) != 0, AB, \
        "0: every join value's owner by hash (no hot table)") \
+    /* CIND check */ \
+    SW(check_lds_slots, Opt<u64>, {}, "RDFIND_CHECK_LDS_SLOTS", opt_u64(v), TEST, \
+       "=<slots>: cap of the condition table rdf_check_cinds stages in LDS (0: always probed in global memory)") \
+    SW(check_records, Opt<u64>, {}, "RDFIND_CHECK_RECORDS", opt_u64(v), TEST, \
+       "=<records>: record budget of one rdf_check_cinds batch (unset: by the free HBM; small: tiny inputs take several batches)") \
     /* failures on request */ \
     SW(test_fail_launch, std::string, {}, "RDFIND_TEST_FAIL_LAUNCH", std::string(v), TEST, \
        "=<kernel>: that kernel is launched with an invalid configuration (k_b2_split)") \
