@@ -60,7 +60,8 @@ RDF_NT_TABS = 1
 # the test-only entry points of rdfind_amd/csrc/test_abi.h (not part of the product ABI)
 TEST_SYMBOLS = ("rdf_test_scan", "rdf_test_scan_batch", "rdf_test_radix", "rdf_test_radix_passes",
                 "rdf_test_radix_segments", "rdf_test_paths", "rdf_test_rewrite_form", "rdf_test_cind_stats_times",
-                "rdf_test_fc_trace", "rdf_test_fc_report", "rdf_test_copy_frequent_unary", "rdf_test_unary_lookup")
+                "rdf_test_fc_trace", "rdf_test_fc_report", "rdf_test_copy_frequent_unary", "rdf_test_unary_lookup",
+                "rdf_test_record_tile", "rdf_test_keep_records", "rdf_test_group_build")
 REWRITE_FORMS = {0: None, 1: "lds", 2: "global"}
 SCAN_U32_U32, SCAN_U32_U64, SCAN_U64_U64 = range(3)
 SCAN_DTYPES = {SCAN_U32_U32: (np.uint32, np.uint32), SCAN_U32_U64: (np.uint32, np.uint64),
@@ -326,6 +327,10 @@ def load():
         "rdf_test_fc_report": (i32, [P, ctypes.POINTER(FcReport)]),
         "rdf_test_copy_frequent_unary": (i32, [P, P, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "rdf_test_unary_lookup": (i32, [P, P, u64, P, P, ctypes.POINTER(u32)]),
+        "rdf_test_record_tile": (ctypes.c_int, []),
+        "rdf_test_keep_records": (i32, [P, P, u64, ctypes.c_int, u64, u32, P, ctypes.POINTER(u64), ctypes.POINTER(u32), P, P,
+                                        P, ctypes.POINTER(u32)]),
+        "rdf_test_group_build": (i32, [P, P, u64, u32, u64, u32, ctypes.POINTER(u64), P, P, P, ctypes.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None) if name in TEST_SYMBOLS else getattr(lib, name)
@@ -867,6 +872,40 @@ class Context:
         self.test_canaries_ok = bool(ok.value)
         self._check(rc, "rdf_test_radix_segments")
         return out[: n_out.value], bool(ok.value)
+
+    def test_record_tile(self) -> int:
+        """Records per tile of the group build's tile kernels (rdf_test_record_tile)."""
+        return int(self._test_fn("rdf_test_record_tile")())
+
+    def test_keep_records(self, keys, joinbits: int, ncap: int, ms: int):
+        """The support and keep passes over sorted records ``capture << joinbits | join`` (rdf_test_keep_records):
+        (support[ncap], dk[Jf], fk[Jf], doff[C + 1], canaries_ok)."""
+        a = np.ascontiguousarray(keys, dtype=np.uint64)
+        sup = np.empty(ncap, np.uint32)
+        dk, fk = np.empty(max(a.shape[0], 1), np.uint64), np.empty(max(a.shape[0], 1), np.uint64)
+        doff = np.empty(ncap + 1, np.uint64)
+        jf, ncomp, ok = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint32()
+        rc = self._test_fn("rdf_test_keep_records")(
+            self.ptr, a.ctypes.data, a.shape[0], joinbits, ncap, ms, sup.ctypes.data, ctypes.byref(jf), ctypes.byref(ncomp),
+            dk.ctypes.data, fk.ctypes.data, doff.ctypes.data, ctypes.byref(ok))
+        self.test_canaries_ok = bool(ok.value)
+        self._check(rc, "rdf_test_keep_records")
+        return sup, dk[: jf.value], fk[: jf.value], doff[: ncomp.value + 1], bool(ok.value)
+
+    def test_group_build(self, fk, num_values: int, rbase=0, gbase=0):
+        """The group passes over records ``join << 32 | capture`` sorted by join (rdf_test_group_build):
+        (goff[G + 1], gcap[n], gmap[num_values], canaries_ok); ``rbase`` / ``gbase``: a join range's offsets."""
+        a = np.ascontiguousarray(fk, dtype=np.uint64)
+        goff = np.empty(a.shape[0] + 1, np.uint64)
+        gcap = np.empty(max(a.shape[0], 1), np.uint32)
+        gmap = np.empty(num_values, np.uint32)
+        g, ok = ctypes.c_uint64(), ctypes.c_uint32()
+        rc = self._test_fn("rdf_test_group_build")(
+            self.ptr, a.ctypes.data, a.shape[0], num_values, rbase, gbase, ctypes.byref(g), goff.ctypes.data,
+            gcap.ctypes.data, gmap.ctypes.data, ctypes.byref(ok))
+        self.test_canaries_ok = bool(ok.value)
+        self._check(rc, "rdf_test_group_build")
+        return goff[: g.value + 1], gcap[: a.shape[0]], gmap, bool(ok.value)
 
     def test_paths(self) -> dict:
         """Which alternative paths the last completed run took (rdf_test_paths): the K1 / K2 / K3 forms by name,

@@ -826,9 +826,6 @@ static constexpr u32 JH_BUCKETS = 1u << JH_BITS;  // join buckets of the join-ra
 //     captures per join value) and capture supports (depCount summed per group,
 //     ALG/operators/candidate_merging/BulkMergeDependencies.scala:78-84)
 
-// Sorted (capture << joinbits | join) records: fresh[i] = keys[i] differs from keys[i - 1] (a distinct
-// (capture, join) pair), and the capture runs' bounds: cstart[c] = first record of capture c, for every
-// c in [0, ncap] (captures without records get the next run's start; cstart[ncap] = n).
 // Streaming kernels over the sorted records take STREAM_U elements per thread per step, their loads issued together
 // (element step * U * T + u * T + thread: every load instruction stays coalesced).  One element per thread per step
 // kept ~16 KB in flight per CU, which at 10^9-triple sizes (arrays far beyond the MALL) held these kernels near
@@ -838,47 +835,115 @@ static constexpr u32 JH_BUCKETS = 1u << JH_BITS;  // join buckets of the join-ra
 #endif
 static constexpr int STREAM_U = RDF_STREAM_U;
 
-static constexpr u64 CSTART_GAP = 64;  // run starts a k_fresh_bounds thread writes per gap of absent captures
-__global__ __launch_bounds__(RDF_BLOCK) void k_fresh_bounds(const u64* __restrict__ keys, u64 n, u64 ncap, int joinbits,
-                                                            u32* fresh, u32* cstart) {
-    const u64 T = (u64)gridDim.x * RDF_BLOCK;
-    for (u64 i0 = (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; i0 <= n; i0 += T * STREAM_U) {
-        u64 k[STREAM_U], kp[STREAM_U];
+// ---- record tiles: ranks of flagged records without per-record flag and scan arrays ------------------------------
+// The kernels that need a record's rank among the flagged ones (fresh records of the (capture, join) order, group
+// heads of the join order) work on tiles of KT_TILE consecutive records, one block per tile: a counting pass writes
+// each tile's number of flagged records, a scan over the tile counts gives the tiles' bases, and the writing pass
+// recomputes the flags from the keys and ranks them inside the tile in registers.  Thread x holds the tile's records
+// u * RDF_BLOCK + x (every load coalesced), so the 64 records of wave w at step u are the tile's segment
+// u * RDF_WAVES_PER_BLOCK + w: a record's in-tile rank = the flagged records of the earlier segments (tile_seg_scan)
+// + those of the lower lanes of its own ballot.  A tile's first record compares with the record before the tile,
+// read from global memory; record 0 is always flagged.
+#ifndef RDF_KT_U
+#define RDF_KT_U 8
+#endif
+static constexpr int KT_U = RDF_KT_U;                         // records per thread per tile
+static constexpr u32 KT_TILE = RDF_BLOCK * KT_U;              // 2048 records
+static constexpr int KT_SEG = KT_U * RDF_WAVES_PER_BLOCK;     // 64-record segments of a tile
+static_assert(KT_SEG <= RDF_WAVE, "one wave scans a tile's segment counts");
+
+__device__ inline int kt_seg(int u) { return u * RDF_WAVES_PER_BLOCK + (int)(threadIdx.x / RDF_WAVE); }
+
+// s_off[s] = flagged records of the tile's segments before s, *s_total = of the whole tile, from the segments'
+// ballots fb[u] (block-wide: two barriers)
+__device__ inline void tile_seg_scan(const u64 (&fb)[KT_U], u32* s_off, u32* s_total) {
+    if (lane_id() == 0) {
 #pragma unroll
-        for (int u = 0; u < STREAM_U; ++u) {
-            const u64 i = i0 + (u64)u * T;
-            k[u] = i < n ? keys[i] : 0ull;
-            kp[u] = i && i <= n ? keys[i - 1] : 0ull;
-        }
+        for (int u = 0; u < KT_U; ++u) s_off[kt_seg(u)] = (u32)__popcll(fb[u]);
+    }
+    __syncthreads();
+    if (threadIdx.x < RDF_WAVE) {
+        const int l = lane_id();
+        const u32 v = l < KT_SEG ? s_off[l] : 0u, incl = wave_inclusive_scan(v);
+        if (l < KT_SEG) s_off[l] = incl - v;
+        if (l == KT_SEG - 1) *s_total = incl;
+    }
+    __syncthreads();
+}
+
+// K5 counting pass over the sorted (capture << joinbits | join) records: a record is fresh when it differs from its
+// predecessor (a distinct (capture, join) pair).  tile_fresh[t] = fresh records of tile t, and support[c] (zeroed by
+// the caller) += the fresh records of capture c's run: the thread at the head of the next run owns a run's count (its
+// own fresh rank minus the previous head's, which the ballots of its segment or the segments' last heads give).  A run
+// between two heads of one tile is stored plainly; only the tile's first and last runs, which may continue in the
+// neighbouring tiles, are added atomically: at most two atomics per tile, however large a capture is.
+__global__ __launch_bounds__(RDF_BLOCK) void k_fresh_bounds(const u64* __restrict__ keys, u64 n, int joinbits,
+                                                            u32* tile_fresh, u32* support) {
+    __shared__ u64 s_fb[KT_SEG], s_hb[KT_SEG];
+    __shared__ u32 s_off[KT_SEG], s_prev[KT_SEG], s_total, s_last;
+    const u64 base = (u64)blockIdx.x * KT_TILE;
+    const int lane = lane_id();
+    u64 k[KT_U], kp[KT_U], fb[KT_U], hb[KT_U];
 #pragma unroll
-        for (int u = 0; u < STREAM_U; ++u) {
-            const u64 i = i0 + (u64)u * T;
-            if (i > n) break;
-            if (i < n) fresh[i] = (i == 0 || kp[u] != k[u]) ? 1u : 0u;
-            const u64 c = i < n ? k[u] >> joinbits : ncap;
-            const u64 cp = i ? (kp[u] >> joinbits) + 1 : 0;
-            // the captures in (previous record's, this record's]: at most CSTART_GAP of them here (the gap's end);
-            // the rest of a longer gap keeps the caller's fill and k_cstart_fix finds it (a thread looping over a
-            // gap of millions of absent captures -- a join range holding only high capture ids -- took 20 ms)
-            for (u64 x = c + 1 > cp + CSTART_GAP ? c + 1 - CSTART_GAP : cp; x <= c; ++x) cstart[x] = (u32)i;
+    for (int u = 0; u < KT_U; ++u) {
+        const u64 i = base + (u64)u * RDF_BLOCK + threadIdx.x;
+        k[u] = i < n ? keys[i] : 0ull;
+        kp[u] = i && i < n ? keys[i - 1] : 0ull;
+    }
+#pragma unroll
+    for (int u = 0; u < KT_U; ++u) {
+        const u64 i = base + (u64)u * RDF_BLOCK + threadIdx.x;
+        fb[u] = __ballot(i < n && (i == 0 || kp[u] != k[u]));
+        hb[u] = __ballot(i < n && (i == 0 || (kp[u] >> joinbits) != (k[u] >> joinbits)));  // first record of a capture
+        if (lane == 0) {
+            s_fb[kt_seg(u)] = fb[u];
+            s_hb[kt_seg(u)] = hb[u];
         }
     }
-}
-
-// run starts k_fresh_bounds left unwritten (cstart filled with ~0 before it): the first record of capture >= x
-__global__ __launch_bounds__(RDF_BLOCK) void k_cstart_fix(const u64* __restrict__ keys, u64 n, u64 ncap, int joinbits,
-                                                          u32* cstart) {
-    for (u64 x = (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; x <= ncap; x += (u64)gridDim.x * RDF_BLOCK)
-        if (cstart[x] == ~0u) cstart[x] = (u32)(x == ncap ? n : lower_bound_u64(keys, n, x << joinbits));
-}
-
-// support of capture c = distinct join values among its records = fresh records of its run; fpos = exclusive
-// scan of the fresh flags (fpos[n] = their total).  No atomics: a hot capture (s[p=rdf:type], in ~every
-// group) is one subtraction.
-__global__ __launch_bounds__(RDF_BLOCK) void k_run_support(const u32* __restrict__ cstart, u64 ncap,
-                                                           const u32* __restrict__ fpos, u32* support) {
-    for (u64 c = (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; c < ncap; c += (u64)gridDim.x * RDF_BLOCK)
-        support[c] = fpos[cstart[c + 1]] - fpos[cstart[c]];
+    __syncthreads();
+    if (threadIdx.x < RDF_WAVE) {
+        const u64 f = lane < KT_SEG ? s_fb[lane] : 0ull, h = lane < KT_SEG ? s_hb[lane] : 0ull;
+        const u32 cnt = (u32)__popcll(f), incl = wave_inclusive_scan(cnt), off = incl - cnt;
+        // the segment's last head: its in-tile fresh rank + 1 (0: no head); ranks ascend, so the last head before a
+        // segment is the maximum over the earlier segments
+        u32 m = h ? off + (u32)__popcll(f & ((1ull << (63 - __clzll((long long)h))) - 1ull)) + 1u : 0u;
+#pragma unroll
+        for (int d = 1; d < RDF_WAVE; d <<= 1) {
+            const u32 t = __shfl_up(m, d, RDF_WAVE);
+            if (lane >= d && t > m) m = t;
+        }
+        const u32 pm = __shfl_up(m, 1, RDF_WAVE);
+        if (lane < KT_SEG) {
+            s_off[lane] = off;
+            s_prev[lane] = lane ? pm : 0u;
+        }
+        if (lane == KT_SEG - 1) {
+            s_total = incl;
+            s_last = m;
+        }
+    }
+    __syncthreads();
+    const u64 lt = lanemask_lt();
+#pragma unroll
+    for (int u = 0; u < KT_U; ++u) {
+        if (!((hb[u] >> lane) & 1ull)) continue;
+        const int s = kt_seg(u);
+        const u32 r = s_off[s] + (u32)__popcll(fb[u] & lt);
+        const u64 hm = hb[u] & lt;
+        const u32 pv = hm ? s_off[s] + (u32)__popcll(fb[u] & ((1ull << (63 - __clzll((long long)hm))) - 1ull)) + 1u : s_prev[s];
+        const u32 cnt = r - (pv ? pv - 1u : 0u);  // 0 only at the tile's first record (no run of this tile ends there)
+        if (cnt) {
+            const u64 cp = kp[u] >> joinbits;
+            if (pv) support[cp] = cnt;
+            else atomicAdd(&support[cp], cnt);
+        }
+    }
+    if (threadIdx.x == 0) {
+        const u32 total = s_total, lv = s_last, cnt = total - (lv ? lv - 1u : 0u);
+        tile_fresh[blockIdx.x] = total;
+        const u64 e = base + KT_TILE < n ? base + KT_TILE : n;
+        if (cnt) atomicAdd(&support[keys[e - 1] >> joinbits], cnt);
+    }
 }
 
 __global__ __launch_bounds__(RDF_BLOCK) void k_support_flags(const u32* __restrict__ support, u64 ncap, u32 ms, u32* flags) {
@@ -906,94 +971,122 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_compact_captures(const u32* __res
 // keep distinct records of frequent captures
 // Fresh records of an infrequent capture are dropped; in (capture, join) order the kept ones of a capture
 // stay contiguous, so a kept record's position is its fresh rank minus the fresh records of the infrequent
-// captures before it.  skipv[c] = this rank's fresh records of c when c is infrequent (global support).
-__global__ __launch_bounds__(RDF_BLOCK) void k_skip_counts(const u32* __restrict__ cstart, const u32* __restrict__ fpos,
-                                                           const u32* __restrict__ support, u64 ncap, u32 ms, u32* skipv) {
+// captures before it.  skipv[c] = this rank's fresh records of c (lcnt: the counting pass's counts of the records at
+// hand -- the supports on one GPU, a rank's or a join range's own counts otherwise) when c is infrequent (global
+// support).
+__global__ __launch_bounds__(RDF_BLOCK) void k_skip_counts(const u32* __restrict__ lcnt, const u32* __restrict__ support,
+                                                           u64 ncap, u32 ms, u32* skipv) {
     for (u64 c = (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; c < ncap; c += (u64)gridDim.x * RDF_BLOCK)
-        skipv[c] = support[c] >= ms ? 0u : fpos[cstart[c + 1]] - fpos[cstart[c]];
+        skipv[c] = support[c] >= ms ? 0u : lcnt[c];
 }
 
 // kept records -> dk = (compact capture << 32 | join) in (capture, join) order (the dependent -> join CSR)
-// and fk = (join << 32 | compact capture) at the same position (sorted by join next, for the groups)
+// and fk = (join << 32 | compact capture) at the same position (sorted by join next, for the groups).
+// One block per record tile: a record's fresh rank = tile_base[tile] (the scanned counts of k_fresh_bounds) + its
+// rank among the tile's fresh records.
 __global__ __launch_bounds__(RDF_BLOCK) void k_keep_scatter(const u64* __restrict__ keys, u64 n, int joinbits,
-                                                            const u32* __restrict__ fpos, const u32* __restrict__ skip,
+                                                            const u32* __restrict__ tile_base, const u32* __restrict__ skip,
                                                             const u32* __restrict__ support, u32 ms,
                                                             const u32* __restrict__ fidx, u64* dk, u64* fk) {
+    __shared__ u32 s_off[KT_SEG], s_total;
     const u64 jmask = (1ull << joinbits) - 1;
-    const u64 T = (u64)gridDim.x * RDF_BLOCK;
-    for (u64 i0 = (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; i0 < n; i0 += T * STREAM_U) {
-        u64 k[STREAM_U], kp[STREAM_U];
+    const u64 base = (u64)blockIdx.x * KT_TILE;
+    u64 k[KT_U], kp[KT_U], fb[KT_U];
 #pragma unroll
-        for (int u = 0; u < STREAM_U; ++u) {
-            const u64 i = i0 + (u64)u * T;
-            k[u] = i < n ? keys[i] : 0ull;
-            kp[u] = i && i < n ? keys[i - 1] : ~k[u];
-        }
+    for (int u = 0; u < KT_U; ++u) {
+        const u64 i = base + (u64)u * RDF_BLOCK + threadIdx.x;
+        k[u] = i < n ? keys[i] : 0ull;
+        kp[u] = i && i < n ? keys[i - 1] : 0ull;
+    }
 #pragma unroll
-        for (int u = 0; u < STREAM_U; ++u) {
-            const u64 i = i0 + (u64)u * T;
-            if (i >= n || kp[u] == k[u]) continue;
-            const u64 cap = k[u] >> joinbits;
-            if (support[cap] < ms) continue;
-            const u64 p = fpos[i] - skip[cap];
-            const u64 c = fidx[cap], j = k[u] & jmask;
-            dk[p] = (c << 32) | j;
-            fk[p] = (j << 32) | c;
-        }
+    for (int u = 0; u < KT_U; ++u) {
+        const u64 i = base + (u64)u * RDF_BLOCK + threadIdx.x;
+        fb[u] = __ballot(i < n && (i == 0 || kp[u] != k[u]));
+    }
+    tile_seg_scan(fb, s_off, &s_total);
+    const u32 tb = tile_base[blockIdx.x];
+    const int lane = lane_id();
+    const u64 lt = lanemask_lt();
+#pragma unroll
+    for (int u = 0; u < KT_U; ++u) {
+        if (!((fb[u] >> lane) & 1ull)) continue;
+        const u64 cap = k[u] >> joinbits;
+        if (support[cap] < ms) continue;
+        const u64 p = tb + s_off[kt_seg(u)] + (u32)__popcll(fb[u] & lt) - skip[cap];
+        const u64 c = fidx[cap], j = k[u] & jmask;
+        dk[p] = (c << 32) | j;
+        fk[p] = (j << 32) | c;
     }
 }
 
-__global__ __launch_bounds__(RDF_BLOCK) void k_group_flags(const u64* __restrict__ fk, u64 n, u32* flags) {
-    const u64 T = (u64)gridDim.x * RDF_BLOCK;
-    for (u64 i0 = (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; i0 < n; i0 += T * STREAM_U) {
-        u64 a[STREAM_U], b[STREAM_U];
+// group heads of the join-sorted fk = (join << 32 | capture): records whose join value differs from the predecessor's.
+// The counting pass: tile_heads[t] = heads of record tile t.
+__global__ __launch_bounds__(RDF_BLOCK) void k_group_flags(const u64* __restrict__ fk, u64 n, u32* tile_heads) {
+    __shared__ u32 s_w[RDF_WAVES_PER_BLOCK];
+    const u64 base = (u64)blockIdx.x * KT_TILE;
+    u32 a[KT_U], b[KT_U];
 #pragma unroll
-        for (int u = 0; u < STREAM_U; ++u) {
-            const u64 i = i0 + (u64)u * T;
-            a[u] = i < n ? fk[i] >> 32 : 0ull;
-            b[u] = i && i < n ? fk[i - 1] >> 32 : ~a[u];
-        }
+    for (int u = 0; u < KT_U; ++u) {
+        const u64 i = base + (u64)u * RDF_BLOCK + threadIdx.x;
+        a[u] = i < n ? (u32)(fk[i] >> 32) : 0u;
+        b[u] = i && i < n ? (u32)(fk[i - 1] >> 32) : 0u;
+    }
+    u32 cnt = 0;  // (the same in every lane of the wave)
 #pragma unroll
-        for (int u = 0; u < STREAM_U; ++u) {
-            const u64 i = i0 + (u64)u * T;
-            if (i < n) flags[i] = a[u] != b[u] ? 1u : 0u;
-        }
+    for (int u = 0; u < KT_U; ++u) {
+        const u64 i = base + (u64)u * RDF_BLOCK + threadIdx.x;
+        cnt += (u32)__popcll(__ballot(i < n && (i == 0 || a[u] != b[u])));
+    }
+    if (lane_id() == 0) s_w[threadIdx.x / RDF_WAVE] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u32 t = 0;
+#pragma unroll
+        for (int w = 0; w < RDF_WAVES_PER_BLOCK; ++w) t += s_w[w];
+        tile_heads[blockIdx.x] = t;
     }
 }
 
-// groups: goff[g] = first record; gcap[i] = compact capture id; gmap[join] = g (fk = join << 32 | capture)
-// STREAM_U elements per thread with their loads in flight together (a one-element grid-stride loop keeps one load per
-// lane in flight and is latency-bound at ~2 TB/s)
-__device__ inline void group_build_body(const u64* __restrict__ fk, u64 n, const u32* __restrict__ gflag,
-                                        const u32* __restrict__ gexcl, u64 rbase, u32 gbase, u64* goff, u32* gcap,
-                                        u32* gmap) {
-    const u64 T = (u64)gridDim.x * RDF_BLOCK;
-    for (u64 i0 = (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; i0 < n; i0 += T * STREAM_U) {
-        u64 k[STREAM_U];
-        u32 f[STREAM_U], x[STREAM_U];
+// groups: goff[gbase + g] = rbase + first record; gcap[rbase + i] = compact capture id; gmap[join] = gbase + g.
+// The writing pass: a head's group = tile_gbase[tile] (the scanned counts of k_group_flags) + its rank among the tile's
+// heads.
+__device__ inline void group_build_body(const u64* __restrict__ fk, u64 n, const u32* __restrict__ tile_gbase, u64 rbase,
+                                        u32 gbase, u64* goff, u32* gcap, u32* gmap) {
+    __shared__ u32 s_off[KT_SEG], s_total;
+    const u64 base = (u64)blockIdx.x * KT_TILE;
+    u64 k[KT_U], hb[KT_U];
+    u32 b[KT_U];
 #pragma unroll
-        for (int u = 0; u < STREAM_U; ++u) {
-            const u64 i = i0 + (u64)u * T;
-            k[u] = i < n ? fk[i] : 0ull;
-            f[u] = i < n ? gflag[i] : 0u;
-            x[u] = i < n ? gexcl[i] : 0u;
-        }
+    for (int u = 0; u < KT_U; ++u) {
+        const u64 i = base + (u64)u * RDF_BLOCK + threadIdx.x;
+        k[u] = i < n ? fk[i] : 0ull;
+        b[u] = i && i < n ? (u32)(fk[i - 1] >> 32) : 0u;
+    }
 #pragma unroll
-        for (int u = 0; u < STREAM_U; ++u) {
-            const u64 i = i0 + (u64)u * T;
-            if (i >= n) break;
-            gcap[rbase + i] = (u32)(k[u] & 0xffffffffu);
-            if (f[u]) {
-                const u32 g = gbase + x[u];
-                goff[g] = rbase + i;
-                gmap[k[u] >> 32] = g;
-            }
+    for (int u = 0; u < KT_U; ++u) {
+        const u64 i = base + (u64)u * RDF_BLOCK + threadIdx.x;
+        hb[u] = __ballot(i < n && (i == 0 || (u32)(k[u] >> 32) != b[u]));
+    }
+    tile_seg_scan(hb, s_off, &s_total);
+    const u32 g0 = gbase + tile_gbase[blockIdx.x];
+    const int lane = lane_id();
+    const u64 lt = lanemask_lt();
+#pragma unroll
+    for (int u = 0; u < KT_U; ++u) {
+        const u64 i = base + (u64)u * RDF_BLOCK + threadIdx.x;
+        if (i >= n) break;
+        gcap[rbase + i] = (u32)(k[u] & 0xffffffffu);
+        if ((hb[u] >> lane) & 1ull) {
+            const u32 g = g0 + s_off[kt_seg(u)] + (u32)__popcll(hb[u] & lt);
+            goff[g] = rbase + i;
+            gmap[k[u] >> 32] = g;
         }
     }
 }
-__global__ __launch_bounds__(RDF_BLOCK) void k_group_build(const u64* __restrict__ fk, u64 n, const u32* __restrict__ gflag,
-                                                           const u32* __restrict__ gexcl, u64* goff, u32* gcap, u32* gmap) {
-    group_build_body(fk, n, gflag, gexcl, 0, 0u, goff, gcap, gmap);
+__global__ __launch_bounds__(RDF_BLOCK) void k_group_build(const u64* __restrict__ fk, u64 n,
+                                                           const u32* __restrict__ tile_gbase, u64* goff, u32* gcap,
+                                                           u32* gmap) {
+    group_build_body(fk, n, tile_gbase, 0, 0u, goff, gcap, gmap);
 }
 
 // dependent -> groups: dgrp[i] = group of the join value of dk[i].  A capture's joins ascend and group ids
@@ -1082,10 +1175,10 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_range_block_counts(const u32* __r
 }
 
 // a range's groups: goff[gbase + g] = rbase + first member, gcap[rbase + i], gmap[join] = gbase + g
-__global__ __launch_bounds__(RDF_BLOCK) void k_group_build_at(const u64* __restrict__ fk, u64 n, const u32* __restrict__ gflag,
-                                                              const u32* __restrict__ gexcl, u64 rbase, u32 gbase, u64* goff,
-                                                              u32* gcap, u32* gmap) {
-    group_build_body(fk, n, gflag, gexcl, rbase, gbase, goff, gcap, gmap);
+__global__ __launch_bounds__(RDF_BLOCK) void k_group_build_at(const u64* __restrict__ fk, u64 n,
+                                                              const u32* __restrict__ tile_gbase, u64 rbase, u32 gbase,
+                                                              u64* goff, u32* gcap, u32* gmap) {
+    group_build_body(fk, n, tile_gbase, rbase, gbase, goff, gcap, gmap);
 }
 
 // a range's dependent -> group entries: dk (compact capture << 32 | join, (capture, join) order) with this range's

@@ -98,7 +98,11 @@ using namespace rdf;
     B(RUN, arcnt) B(RUN, ar_bits) B(RUN, ar_rules) B(RUN, arref) \
     /* capture groups */ \
     B(SPARE_GROUPS, rec) B(SPARE_GROUPS, rec_tmp) B(RUN, support) B(RUN, fidx) B(RUN, fcap) B(RUN, info) \
-    B(SPARE_GROUPS, fk) B(SPARE_GROUPS, fk_tmp) B(RUN, fpos) B(RUN, cstart) B(RUN, skip) B(RUN, gflag) B(RUN, gexcl) \
+    /* per record tile (KT_TILE records, kernels.inl): the fresh records of the (capture, join)-sorted records and */ \
+    /* their scan, the group heads of the join-sorted kept records and their scan (4 B per tile each).  fpos, gflag */ \
+    /* and gexcl are scratch of other stages (the frequent conditions' and the rules' scans, the dense light groups) */ \
+    B(SPARE_GROUPS, fk) B(SPARE_GROUPS, fk_tmp) B(RUN, tile_fresh) B(RUN, tile_base) B(RUN, tile_heads) B(RUN, tile_gbase) \
+    B(RUN, skip) B(RUN, fpos) B(RUN, gflag) B(RUN, gexcl) \
     B(RUN, goff) B(RUN, gcap) B(RUN, gmap) B(RUN, csup) B(RUN, doff) B(RUN, dcur) B(RUN, dgrp) \
     B(RUN, hist) B(RUN, heavy_list) B(RUN, hbit) B(RUN, bcomp) B(RUN, bkeyc) B(RUN, pcnt) B(RUN, poff) B(RUN, pcur) \
     B(RUN, plist) \
@@ -2135,8 +2139,8 @@ static JoinSel shard_sel(const rdf_ctx* c) {
     return js;
 }
 
-// K3 emission of the selected join values (record buffers of cap_rec slots), K4 sort by (capture, join), K5 run
-// bounds (cstart), fresh-record scan (fpos) and the records' supports -> sup[ncap].  The sorted records are left in
+// K3 emission of the selected join values (record buffers of cap_rec slots), K4 sort by (capture, join), K5 fresh
+// records per record tile (tile_fresh, tile_base) and the records' supports -> sup[ncap].  The sorted records are left in
 // c->rec_sorted; *Jout = their number.  Adds to c->J_emit and c->sort_passes_records.
 // Join ranges (g_build_ranges) emit every range twice with the same selection: the first emission (cache = +1 + k,
 // range k) keeps the scanned per-block offsets and the slot count, the second (cache = -1 - k) reuses them instead of
@@ -2313,14 +2317,20 @@ static rdf_status g_emit_range(rdf_ctx* c, int proj, JoinSel js, u64 cap_rec, u3
     return g_sort_support(c, ebuf, c->rec_tmp.as<u64>(), Je, sup, Jout, nullptr);
 }
 
-// fresh-record flags (c->flags) and capture run starts (c->cstart[0, ncap]) of J sorted records
-static rdf_status g_fresh_bounds(rdf_ctx* c, const u64* keys, u64 J) {
+// record tiles of n records (one block each; n < 2^32)
+static inline unsigned rec_tiles(u64 n) { return (unsigned)((n + KT_TILE - 1) / KT_TILE); }
+
+// K5 counting pass over J sorted records: sup[0, ncap) = fresh records per capture (distinct join values), the fresh
+// records per record tile (c->tile_fresh) and their scan (c->tile_base; [tiles] = the fresh records of all)
+static rdf_status g_fresh_bounds(rdf_ctx* c, const u64* keys, u64 J, u32* sup) {
     hipStream_t st = c->stream;
-    HIP_TRY(c, hipMemsetAsync(c->cstart.p, 0xff, (c->ncap + 1) * 4, st));
-    hipLaunchKernelGGL(k_fresh_bounds, dim3(grid_for(J + 1, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, keys, J, c->ncap,
-                       c->joinbits, c->flags.as<u32>(), c->cstart.as<u32>());
-    hipLaunchKernelGGL(k_cstart_fix, dim3(grid_for(c->ncap + 1, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, keys, J, c->ncap,
-                       c->joinbits, c->cstart.as<u32>());
+    const unsigned nt = rec_tiles(J);
+    ENSURE(c, tile_fresh, std::max<u64>(nt, 1) * 4);
+    ENSURE(c, tile_base, (nt + 1ull) * 4);
+    HIP_TRY(c, hipMemsetAsync(sup, 0, std::max<u64>(c->ncap, 1) * 4, st));
+    if (nt)
+        hipLaunchKernelGGL(k_fresh_bounds, dim3(nt), dim3(RDF_BLOCK), 0, st, keys, J, c->joinbits, c->tile_fresh.as<u32>(), sup);
+    HIP_TRY(c, exclusive_scan_u32(c->ws, c->tile_fresh.as<u32>(), c->tile_base.as<u32>(), nt, c->tile_base.as<u32>() + nt, st));
     return RDF_OK;
 }
 
@@ -2345,20 +2355,11 @@ static rdf_status g_sort_support(rdf_ctx* c, u64* keys, u64* tmp, u64 Je, u32* s
 
 // K5 supports of J sorted records -> sup.  Sets c->rec_sorted, *Jout.
 static rdf_status g_support_sorted(rdf_ctx* c, u64* keys, u64 J, u32* sup, u64* Jout) {
-    hipStream_t st = c->stream;
-    const u64 ncap = c->ncap;
     *Jout = J;
     c->rec_sorted = keys;
     // supports = distinct join values per capture: fresh (capture, join) records counted per key run
-    ENSURE(c, flags, std::max<u64>(J, 1) * 4);
-    ENSURE(c, fpos, (J + 1) * 4);
-    ENSURE(c, cstart, (ncap + 1) * 4);
     tbegin(c, RDF_T_SUPPORT);
-    TRY(g_fresh_bounds(c, keys, J));
-    HIP_TRY(c, exclusive_scan_u32(c->ws, c->flags.as<u32>(), c->fpos.as<u32>(), J, c->fpos.as<u32>() + J, st));
-    if (ncap)
-        hipLaunchKernelGGL(k_run_support, dim3(grid_for(ncap, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->cstart.as<u32>(),
-                           ncap, c->fpos.as<u32>(), sup);
+    TRY(g_fresh_bounds(c, keys, J, sup));
     tend(c, RDF_T_SUPPORT);
     return RDF_OK;
 }
@@ -2406,71 +2407,84 @@ static rdf_status g_compact_captures(rdf_ctx* c) {
     return RDF_OK;
 }
 
-// frequent-capture compaction (c->support = global supports), capture groups, dependent -> groups CSR
-static rdf_status g_compact_groups(rdf_ctx* c) {
+// group heads of Jr join-sorted kept records (c->fk): the heads per record tile (c->tile_heads), their scan
+// (c->tile_gbase) and the number of groups -> *Gout (one read-back)
+static rdf_status g_group_heads(rdf_ctx* c, u64 Jr, u32* Gout) {
+    hipStream_t st = c->stream;
+    const unsigned nt = rec_tiles(Jr);
+    ENSURE(c, tile_heads, std::max<u64>(nt, 1) * 4);
+    ENSURE(c, tile_gbase, (nt + 1ull) * 4);
+    if (nt) hipLaunchKernelGGL(k_group_flags, dim3(nt), dim3(RDF_BLOCK), 0, st, c->fk.as<u64>(), Jr, c->tile_heads.as<u32>());
+    HIP_TRY(c, exclusive_scan_u32(c->ws, c->tile_heads.as<u32>(), c->tile_gbase.as<u32>(), nt, c->tile_gbase.as<u32>() + nt, st));
+    return read_u32(c, c->tile_gbase.as<u32>() + nt, Gout);
+}
+
+// frequent-capture compaction (c->support = global supports), capture groups, dependent -> groups CSR.  local_sup
+// (sharded: this rank's supports, as the counting pass left them before the all-reduce) gives each capture's fresh
+// records here, nullptr = its global support (one GPU)
+static rdf_status g_compact_groups(rdf_ctx* c, const u32* local_sup) {
     hipStream_t st = c->stream;
     const u32 V = c->V ? c->V : 1;
     const u64 ncap = c->ncap, J = c->J;
     const int joinbits = c->joinbits;
     u64* keys = c->rec_sorted;
     tbegin(c, RDF_T_SUPPORT);
-    ENSURE(c, flags, std::max(J, ncap) * 4);
     TRY(g_compact_captures(c));
     const u32 C = c->C;
     // distinct records of frequent captures -> dk = (compact capture << 32 | join) in (capture, join) order,
     // written to the record buffer that does not hold the sorted keys
     ENSURE(c, skip, (ncap + 1) * 4);
     if (ncap)
-        hipLaunchKernelGGL(k_skip_counts, dim3(grid_for(ncap, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->cstart.as<u32>(),
-                           c->fpos.as<u32>(), c->support.as<u32>(), ncap, c->ms, c->flags.as<u32>());
+        hipLaunchKernelGGL(k_skip_counts, dim3(grid_for(ncap, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st,
+                           local_sup ? local_sup : c->support.as<u32>(), c->support.as<u32>(), ncap, c->ms, c->flags.as<u32>());
     HIP_TRY(c, exclusive_scan_u32(c->ws, c->flags.as<u32>(), c->skip.as<u32>(), ncap, c->skip.as<u32>() + ncap, st));
+    const unsigned nt = rec_tiles(J);
     u64 fs[2];
-    TRY(read_multi(c, {{c->fpos.as<u32>() + J, 4}, {c->skip.as<u32>() + ncap, 4}}, fs));
+    TRY(read_multi(c, {{c->tile_base.as<u32>() + nt, 4}, {c->skip.as<u32>() + ncap, 4}}, fs));
     const u64 Jf = fs[0] - fs[1];
     c->Jf = Jf;
     u64* dk = keys == c->rec.as<u64>() ? c->rec_tmp.as<u64>() : c->rec.as<u64>();
     ENSURE(c, fk, std::max<u64>(Jf, 1) * 8);
     ENSURE(c, fk_tmp, std::max<u64>(Jf, 1) * 8);
-    if (J)
-        hipLaunchKernelGGL(k_keep_scatter, dim3(grid_for(J, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, keys, J, joinbits,
-                           c->fpos.as<u32>(), c->skip.as<u32>(), c->support.as<u32>(), c->ms, c->fidx.as<u32>(), dk,
-                           c->fk.as<u64>());
+    if (nt)
+        hipLaunchKernelGGL(k_keep_scatter, dim3(nt), dim3(RDF_BLOCK), 0, st, keys, J, joinbits, c->tile_base.as<u32>(),
+                           c->skip.as<u32>(), c->support.as<u32>(), c->ms, c->fidx.as<u32>(), dk, c->fk.as<u64>());
     tend(c, RDF_T_SUPPORT);
     tbegin(c, RDF_T_GROUPS);
-    // dependent -> join offsets straight from dk; groups need the (join, capture) order: a stable sort of
-    // fk = (join << 32 | capture) on the join bits keeps each group's captures ascending
+    // dependent -> join offsets: the scan of the frequent captures' kept records (one per join value: the support, on a
+    // rank its local support); groups need the (join, capture) order: a stable sort of fk = (join << 32 | capture) on
+    // the join bits keeps each group's captures ascending
     ENSURE(c, csup, std::max<u64>(C, 1) * 4);
     ENSURE(c, doff, (C + 1ull) * 8);
     ENSURE(c, dgrp, std::max<u64>(Jf, 1) * 4);
     if (C)
         hipLaunchKernelGGL(k_info_support_u32, dim3(grid_for(C, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st,
                            c->info.as<CapInfo>(), C, c->csup.as<u32>());
+    const u32* nrec = c->csup.as<u32>();
+    if (local_sup) {
+        ENSURE(c, dcur, std::max<u64>(C, 1) * 4);  // (scratch here: the range build's cursor)
+        if (C)
+            hipLaunchKernelGGL(k_gather_u32, dim3(grid_for(C, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, local_sup,
+                               c->fcap.as<u32>(), (u64)C, c->dcur.as<u32>());
+        nrec = c->dcur.as<u32>();
+    }
+    HIP_TRY(c, exclusive_scan_u32_u64(c->ws, nrec, c->doff.as<u64>(), C, c->doff.as<u64>() + C, st));
     if (Jf) {
-        hipLaunchKernelGGL(k_key_offsets, dim3(grid_for(C + 1ull, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, dk, Jf, C,
-                           c->doff.as<u64>());
         u64* tk = c->fk.as<u64>();
         u64* tt = c->fk_tmp.as<u64>();
         HIP_TRY(c, radix_sort_u64_bits(c->ws, tk, tt, Jf, 32, 32 + joinbits, st));
         if (tk != c->fk.as<u64>()) std::swap(c->fk, c->fk_tmp);
-    } else {
-        HIP_TRY(c, hipMemsetAsync(c->doff.p, 0, (C + 1ull) * 8, st));
     }
-    ENSURE(c, gflag, std::max<u64>(Jf, 1) * 4);
-    ENSURE(c, gexcl, (Jf + 1) * 4);
-    if (Jf)
-        hipLaunchKernelGGL(k_group_flags, dim3(grid_for(Jf, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->fk.as<u64>(), Jf,
-                           c->gflag.as<u32>());
-    HIP_TRY(c, exclusive_scan_u32(c->ws, c->gflag.as<u32>(), c->gexcl.as<u32>(), Jf, c->gexcl.as<u32>() + Jf, st));
     u32 G32 = 0;
-    TRY(read_u32(c, c->gexcl.as<u32>() + Jf, &G32));
+    TRY(g_group_heads(c, Jf, &G32));
     const u64 G = G32;
     c->G = G;
     ENSURE(c, goff, (G + 1) * 8);
     ENSURE(c, gcap, std::max<u64>(Jf, 1) * 4 + 16);  // + 16 B: the light pass reads whole aligned quads
     ENSURE(c, gmap, (u64)V * 4);
     if (Jf) {
-        hipLaunchKernelGGL(k_group_build, dim3(grid_for(Jf, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->fk.as<u64>(), Jf,
-                           c->gflag.as<u32>(), c->gexcl.as<u32>(), c->goff.as<u64>(), c->gcap.as<u32>(), c->gmap.as<u32>());
+        hipLaunchKernelGGL(k_group_build, dim3(rec_tiles(Jf)), dim3(RDF_BLOCK), 0, st, c->fk.as<u64>(), Jf,
+                           c->tile_gbase.as<u32>(), c->goff.as<u64>(), c->gcap.as<u32>(), c->gmap.as<u32>());
         hipLaunchKernelGGL(k_dgrp, dim3(grid_for(Jf, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, dk, Jf, c->gmap.as<u32>(),
                            c->dgrp.as<u32>());
     }
@@ -2679,18 +2693,14 @@ static rdf_status g_ranges_supports(rdf_ctx* c, int proj, u64 max_range, JoinSel
     return RDF_OK;
 }
 
-// pass 2 of a kept range: its sorted records from rstore, their run bounds (cstart) and fresh-record scan (fpos)
+// pass 2 of a kept range: its sorted records from rstore, their fresh records per capture (c->rsup) and per record
+// tile (g_fresh_bounds)
 static rdf_status g_restore_range(rdf_ctx* c, size_t k, u64* Jout) {
-    hipStream_t st = c->stream;
-    const u64 J = c->jr_J[k], ncap = c->ncap;
+    const u64 J = c->jr_J[k];
     u64* keys = c->rstore.as<u64>() + c->jr_seg[k];
-    ENSURE(c, flags, std::max<u64>(J, 1) * 4);
-    ENSURE(c, fpos, (J + 1) * 4);
-    ENSURE(c, cstart, (ncap + 1) * 4);
     ENSURE(c, rec, std::max<u64>(c->jr_cap_rec, 1) * 8);  // the kept records' destination (dk) in pass 2
     tbegin(c, RDF_T_SUPPORT);
-    TRY(g_fresh_bounds(c, keys, J));
-    HIP_TRY(c, exclusive_scan_u32(c->ws, c->flags.as<u32>(), c->fpos.as<u32>(), J, c->fpos.as<u32>() + J, st));
+    TRY(g_fresh_bounds(c, keys, J, c->rsup.as<u32>()));
     tend(c, RDF_T_SUPPORT);
     c->rec_sorted = keys;
     *Jout = J;
@@ -2749,21 +2759,22 @@ static rdf_status g_ranges_groups(rdf_ctx* c, int proj, JoinSel own, const u32* 
         else TRY(g_emit_range(c, proj, js, cap_rec, c->rsup.as<u32>(), &J, -1 - (int)k));
         u64* keys = c->rec_sorted;
         tbegin(c, RDF_T_SUPPORT);
-        ENSURE(c, flags, std::max<u64>(std::max<u64>(J, ncap), 1) * 4);
+        // (c->rsup: this range's fresh records per capture, as its emission or g_restore_range just counted them)
+        ENSURE(c, flags, std::max<u64>(ncap, 1) * 4);
         if (ncap)
-            hipLaunchKernelGGL(k_skip_counts, dim3(grid_for(ncap, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->cstart.as<u32>(),
-                               c->fpos.as<u32>(), c->support.as<u32>(), ncap, c->ms, c->flags.as<u32>());
+            hipLaunchKernelGGL(k_skip_counts, dim3(grid_for(ncap, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->rsup.as<u32>(),
+                               c->support.as<u32>(), ncap, c->ms, c->flags.as<u32>());
         HIP_TRY(c, exclusive_scan_u32(c->ws, c->flags.as<u32>(), c->skip.as<u32>(), ncap, c->skip.as<u32>() + ncap, st));
+        const unsigned nt = rec_tiles(J);
         u64 fs[2];
-        TRY(read_multi(c, {{c->fpos.as<u32>() + J, 4}, {c->skip.as<u32>() + ncap, 4}}, fs));
+        TRY(read_multi(c, {{c->tile_base.as<u32>() + nt, 4}, {c->skip.as<u32>() + ncap, 4}}, fs));
         const u64 Jr = fs[0] - fs[1];  // this range's kept records
         u64* dk = keys == c->rec.as<u64>() ? c->rec_tmp.as<u64>() : c->rec.as<u64>();
         ENSURE(c, fk, std::max<u64>(Jr, 1) * 8);
         ENSURE(c, fk_tmp, std::max<u64>(Jr, 1) * 8);
-        if (J)
-            hipLaunchKernelGGL(k_keep_scatter, dim3(grid_for(J, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, keys, J, joinbits,
-                               c->fpos.as<u32>(), c->skip.as<u32>(), c->support.as<u32>(), c->ms, c->fidx.as<u32>(), dk,
-                               c->fk.as<u64>());
+        if (nt)
+            hipLaunchKernelGGL(k_keep_scatter, dim3(nt), dim3(RDF_BLOCK), 0, st, keys, J, joinbits, c->tile_base.as<u32>(),
+                               c->skip.as<u32>(), c->support.as<u32>(), c->ms, c->fidx.as<u32>(), dk, c->fk.as<u64>());
         tend(c, RDF_T_SUPPORT);
         tbegin(c, RDF_T_GROUPS);
         if (Jr) {
@@ -2772,19 +2783,12 @@ static rdf_status g_ranges_groups(rdf_ctx* c, int proj, JoinSel own, const u32* 
             HIP_TRY(c, radix_sort_u64_bits(c->ws, tk, tt, Jr, 32, 32 + joinbits, st));
             if (tk != c->fk.as<u64>()) std::swap(c->fk, c->fk_tmp);
         }
-        ENSURE(c, gflag, std::max<u64>(Jr, 1) * 4);
-        ENSURE(c, gexcl, (Jr + 1) * 4);
-        if (Jr)
-            hipLaunchKernelGGL(k_group_flags, dim3(grid_for(Jr, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->fk.as<u64>(), Jr,
-                               c->gflag.as<u32>());
-        HIP_TRY(c, exclusive_scan_u32(c->ws, c->gflag.as<u32>(), c->gexcl.as<u32>(), Jr, c->gexcl.as<u32>() + Jr, st));
         u32 Gr = 0;
-        TRY(read_u32(c, c->gexcl.as<u32>() + Jr, &Gr));
+        TRY(g_group_heads(c, Jr, &Gr));
         if (G0 + Gr > Gmax || Jf0 + Jr > Jf) return fail(c, RDF_ERR_LIMIT, "join ranges disagree on the kept records");
         if (Jr) {
-            hipLaunchKernelGGL(k_group_build_at, dim3(grid_for(Jr, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->fk.as<u64>(), Jr,
-                               c->gflag.as<u32>(), c->gexcl.as<u32>(), Jf0, (u32)G0, c->goff.as<u64>(), c->gcap.as<u32>(),
-                               c->gmap.as<u32>());
+            hipLaunchKernelGGL(k_group_build_at, dim3(rec_tiles(Jr)), dim3(RDF_BLOCK), 0, st, c->fk.as<u64>(), Jr,
+                               c->tile_gbase.as<u32>(), Jf0, (u32)G0, c->goff.as<u64>(), c->gcap.as<u32>(), c->gmap.as<u32>());
             hipLaunchKernelGGL(k_key_offsets, dim3(grid_for(C + 1ull, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, dk, Jr, C,
                                c->offp.as<u64>());
             hipLaunchKernelGGL(k_dgrp_range, dim3(grid_for(Jr, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, dk, Jr,
@@ -2815,11 +2819,12 @@ static rdf_status g_build_ranges(rdf_ctx* c, int proj, u64 max_range) {
     return g_ranges_groups(c, proj, all, nullptr);
 }
 
-// records per join range of the automatic g_build_ranges: the range scratch (two record buffers, fresh flags + scan,
-// kept keys and their sort buffer, group flags + scan: <= 48 B per record) in the free HBM left after the stage's
+// records per join range of the automatic g_build_ranges: the range scratch (two record buffers, kept keys and
+// their sort buffer: 32 B per record since the per-record flag and scan arrays went; the budget below keeps the
+// earlier 48 B until a run at 10^9 triples shows what it can give back) in the free HBM left after the stage's
 // global arrays (gcap + dgrp, <= 8 B per record overall), at most 2^31.  This sizes the ranges only: a range is
 // consecutive 2^(joinbits-14)-value join buckets, so one bucket larger than this (hot join values) makes a larger
-// range; the hard bound is the u32 record offsets inside a range (cstart, fpos: < 2^32 - 1 records, checked with
+// range; the hard bound is the u32 record offsets inside a range (tile_base, skip: < 2^32 - 1 records, checked with
 // RDF_ERR_LIMIT), and a range's buffers are sized by the largest range (an allocation failure is RDF_ERR_OOM)
 static u64 auto_range_records(rdf_ctx* c) {
     size_t free_b = 0, total_b = 0;
@@ -2978,7 +2983,7 @@ rdf_status rdf_build_capture_groups(rdf_ctx* c, const char* projection, rdf_grou
         TRY(g_build_ranges(c, proj, c->sw.group_range_records ? c->sw.group_range_records : auto_range_records(c)));
     } else {
         TRY(g_emit_sort_support(c, proj));
-        TRY(g_compact_groups(c));
+        TRY(g_compact_groups(c, nullptr));
     }
     if (c->ar_on) TRY(g_ar_refs(c));
     TRY(g_size_hist(c, nullptr));
@@ -4684,12 +4689,12 @@ static rdf_status sh_phase14(rdf_ctx* c, rdf_exchange* req) {
         if (c->sh_ranged) {
             TRY(g_ranges_supports(c, c->sh_proj, c->sw.group_range_records ? c->sw.group_range_records : auto_range_records(c),
                                   shard_sel(c)));
-            // this rank's supports, kept for pass 2 (the all-reduce brings the global ones)
-            ENSURE(c, lsup, std::max<u64>(c->ncap, 1) * 4);
-            HIP_TRY(c, hipMemcpyAsync(c->lsup.p, c->support.p, std::max<u64>(c->ncap, 1) * 4, hipMemcpyDeviceToDevice, st));
         } else {
             TRY(g_emit_sort_support(c, c->sh_proj));
         }
+        // this rank's supports, kept for the kept records' positions (the all-reduce brings the global ones)
+        ENSURE(c, lsup, std::max<u64>(c->ncap, 1) * 4);
+        HIP_TRY(c, hipMemcpyAsync(c->lsup.p, c->support.p, std::max<u64>(c->ncap, 1) * 4, hipMemcpyDeviceToDevice, st));
     }
     HIP_TRY(c, hipStreamSynchronize(st));
     return x_request(c, req, RDF_X_ALLREDUCE_SUM_U32, c->support.p, c->ncap, 1);
@@ -4701,7 +4706,7 @@ static rdf_status sh_phase1(rdf_ctx* c, rdf_exchange* req) {
         ReceivedTriples rt(c);
         TRY(g_ranges_groups(c, c->sh_proj, shard_sel(c), c->lsup.as<u32>()));
     } else {
-        TRY(g_compact_groups(c));
+        TRY(g_compact_groups(c, c->lsup.as<u32>()));
     }
     c->spare_x = false;  // the exchange buffers carry the collectives again
     if (c->ar_on) TRY(g_ar_refs(c));

@@ -70,6 +70,32 @@ rdf_status rdf_test_radix_segments(rdf_ctx* ctx, const uint64_t* src_host, uint6
                                    int32_t hist_bump, uint32_t hist_bump_seg, uint32_t hist_bump_digit,
                                    uint64_t* out_host, uint64_t* n_out, uint32_t* canaries_ok);
 
+/* The record-tile kernels of the group build (kernels.inl: k_fresh_bounds, k_keep_scatter, k_group_flags,
+ * k_group_build) on caller data, every device array between canaries; no pipeline state is read or written.
+ *
+ * rdf_test_record_tile: records per tile (the kernels' edges lie at its multiples). */
+int rdf_test_record_tile(void);
+
+/* The support and keep passes over n sorted records keys_host[i] = capture << joinbits | join (capture < ncap, join <
+ * 2^joinbits, 1 <= joinbits <= 32; unsorted keys are refused, RDF_ERR_ARG): support_out[0, ncap) = distinct join values
+ * per capture; the captures with support >= ms are frequent, *C_out of them, numbered in ascending order; *Jf_out =
+ * the distinct records of frequent captures, dk_out[0, Jf) = compact capture << 32 | join in (capture, join) order,
+ * fk_out[0, Jf) = join << 32 | compact capture at the same positions; doff_out[0, C] = each compact capture's first
+ * position in dk (doff_out[C] = Jf).  dk_out and fk_out hold n entries, doff_out ncap + 1. */
+rdf_status rdf_test_keep_records(rdf_ctx* ctx, const uint64_t* keys_host, uint64_t n, int joinbits, uint64_t ncap,
+                                 uint32_t ms, uint32_t* support_out, uint64_t* Jf_out, uint32_t* C_out, uint64_t* dk_out,
+                                 uint64_t* fk_out, uint64_t* doff_out, uint32_t* canaries_ok);
+
+/* The group passes over n records fk_host[i] = join << 32 | capture sorted by join value (join < V; refused otherwise):
+ * *G_out = distinct join values; goff_out[0, G] = rbase + each group's first record (goff_out[G] = rbase + n);
+ * gcap_out[0, n) = the records' captures; gmap_out[0, V): gbase + the group of every join value that occurs, the fill
+ * pattern (RDF_TEST_CANARY_BYTE) elsewhere.  rbase / gbase: the offsets of a join range's records and groups in the
+ * whole arrays (k_group_build_at; both 0: k_group_build); nothing before them may be written.  goff_out holds n + 1
+ * entries. */
+rdf_status rdf_test_group_build(rdf_ctx* ctx, const uint64_t* fk_host, uint64_t n, uint32_t V, uint64_t rbase,
+                                uint32_t gbase, uint64_t* G_out, uint64_t* goff_out, uint32_t* gcap_out, uint32_t* gmap_out,
+                                uint32_t* canaries_ok);
+
 /* Paths of the last completed run (RDF_ERR_STATE without one).  0 in a form field: that stage made no choice
  * (K2 and K3 of an input without triples). */
 enum { RDF_TEST_K1_PARTITIONED = 1, RDF_TEST_K1_RADIX = 2, RDF_TEST_K1_ATOMIC = 3 };

@@ -260,6 +260,156 @@ rdf_status rdf_test_radix_segments(rdf_ctx* c, const uint64_t* src_host, uint64_
     return RDF_OK;
 }
 
+int rdf_test_record_tile(void) { return (int)KT_TILE; }
+
+rdf_status rdf_test_keep_records(rdf_ctx* c, const uint64_t* keys_host, uint64_t n, int joinbits, uint64_t ncap, uint32_t ms,
+                                 uint32_t* support_out, uint64_t* Jf_out, uint32_t* C_out, uint64_t* dk_out, uint64_t* fk_out,
+                                 uint64_t* doff_out, uint32_t* canaries_ok) {
+    if (!c) return RDF_ERR_ARG;
+    if (!canaries_ok || !support_out || !Jf_out || !C_out || !doff_out || (n && (!keys_host || !dk_out || !fk_out)))
+        return fail(c, RDF_ERR_ARG, "rdf_test_keep_records: null argument");
+    *canaries_ok = 0;
+    *Jf_out = 0;
+    *C_out = 0;
+    if (joinbits < 1 || joinbits > 32 || ncap < 1 || ncap >= (1ull << 31) || n >= (1ull << 32) || ms < 1)
+        return fail(c, RDF_ERR_ARG, "rdf_test_keep_records: joinbits, ncap, n or ms out of range");
+    for (u64 i = 0; i < n; ++i)
+        if ((keys_host[i] >> joinbits) >= ncap || (i && keys_host[i] < keys_host[i - 1]))
+            return fail(c, RDF_ERR_ARG, "rdf_test_keep_records: the keys are not sorted or name a capture >= ncap");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const unsigned nt = (unsigned)((n + KT_TILE - 1) / KT_TILE);
+    TestArr keys, sup, tfresh, tbase, flags, fidx, skip, fcap, info, csup, doff, dk, fk;
+    HIP_TRY(c, keys.make(8, n, 0, st));
+    HIP_TRY(c, sup.make(4, ncap, 0, st));
+    HIP_TRY(c, tfresh.make(4, nt, 0, st));
+    HIP_TRY(c, tbase.make(4, nt + 1ull, 0, st));
+    HIP_TRY(c, flags.make(4, ncap, 0, st));
+    HIP_TRY(c, fidx.make(4, ncap + 1, 0, st));
+    HIP_TRY(c, skip.make(4, ncap + 1, 0, st));
+    if (n) HIP_TRY(c, hipMemcpyAsync(keys.data(), keys_host, n * 8, hipMemcpyHostToDevice, st));
+    const unsigned gc = grid_for(ncap, RDF_BLOCK, kGrid);
+    // the counting pass and its scan (g_fresh_bounds)
+    HIP_TRY(c, hipMemsetAsync(sup.data(), 0, ncap * 4, st));
+    if (nt)
+        hipLaunchKernelGGL(k_fresh_bounds, dim3(nt), dim3(RDF_BLOCK), 0, st, (const u64*)keys.data(), n, joinbits,
+                           (u32*)tfresh.data(), (u32*)sup.data());
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        e = exclusive_scan_u32(c->ws, (const u32*)tfresh.data(), (u32*)tbase.data(), nt, (u32*)tbase.data() + nt, st);
+    // the frequent captures' compact ids (g_compact_captures) and the infrequent ones' fresh records before each capture
+    hipLaunchKernelGGL(k_support_flags, dim3(gc), dim3(RDF_BLOCK), 0, st, (const u32*)sup.data(), ncap, ms, (u32*)flags.data());
+    if (e == hipSuccess)
+        e = exclusive_scan_u32(c->ws, (const u32*)flags.data(), (u32*)fidx.data(), ncap, (u32*)fidx.data() + ncap, st);
+    hipLaunchKernelGGL(k_skip_counts, dim3(gc), dim3(RDF_BLOCK), 0, st, (const u32*)sup.data(), (const u32*)sup.data(), ncap, ms,
+                       (u32*)flags.data());
+    if (e == hipSuccess)
+        e = exclusive_scan_u32(c->ws, (const u32*)flags.data(), (u32*)skip.data(), ncap, (u32*)skip.data() + ncap, st);
+    u32 h[3] = {0, 0, 0};  // fresh records, those of infrequent captures, frequent captures
+    if (e == hipSuccess) e = hipMemcpyAsync(&h[0], (u32*)tbase.data() + nt, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h[1], (u32*)skip.data() + ncap, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h[2], (u32*)fidx.data() + ncap, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    TRY(prim_status(c, e, "rdf_test_keep_records (counting pass)"));
+    if (h[1] > h[0] || h[0] > n || h[2] > ncap) return fail(c, RDF_ERR_HIP, "rdf_test_keep_records: counts out of range");
+    const u64 Jf = h[0] - h[1];
+    const u32 C = h[2];
+    HIP_TRY(c, fcap.make(4, C, 0, st));
+    HIP_TRY(c, info.make(sizeof(CapInfo), C, 0, st));
+    HIP_TRY(c, csup.make(4, C, 0, st));
+    HIP_TRY(c, doff.make(8, C + 1ull, 0, st));
+    HIP_TRY(c, dk.make(8, Jf, 0, st));
+    HIP_TRY(c, fk.make(8, Jf, 0, st));
+    hipLaunchKernelGGL(k_compact_captures, dim3(gc), dim3(RDF_BLOCK), 0, st, (const u32*)sup.data(), (const u32*)fidx.data(), ncap,
+                       ms, (u32*)fcap.data(), (CapInfo*)info.data());
+    // the writing pass, and the dependents' offsets from the frequent captures' record counts (g_compact_groups)
+    if (nt)
+        hipLaunchKernelGGL(k_keep_scatter, dim3(nt), dim3(RDF_BLOCK), 0, st, (const u64*)keys.data(), n, joinbits,
+                           (const u32*)tbase.data(), (const u32*)skip.data(), (const u32*)sup.data(), ms, (const u32*)fidx.data(),
+                           (u64*)dk.data(), (u64*)fk.data());
+    if (C)
+        hipLaunchKernelGGL(k_info_support_u32, dim3(grid_for(C, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st,
+                           (const CapInfo*)info.data(), C, (u32*)csup.data());
+    e = hipGetLastError();
+    if (e == hipSuccess)
+        e = exclusive_scan_u32_u64(c->ws, (const u32*)csup.data(), (u64*)doff.data(), C, (u64*)doff.data() + C, st);
+    HIP_TRY(c, hipStreamSynchronize(st));
+    bool ok = true;
+    for (const TestArr* a : {&keys, &sup, &tfresh, &tbase, &flags, &fidx, &skip, &fcap, &info, &csup, &doff, &dk, &fk})
+        HIP_TRY(c, check_canaries(*a, &ok));
+    HIP_TRY(c, check_contents(keys, keys_host, n, &ok));  // the records are read only
+    *canaries_ok = ok ? 1 : 0;
+    TRY(prim_status(c, e, "rdf_test_keep_records"));
+    HIP_TRY(c, hipMemcpy(support_out, sup.data(), ncap * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(doff_out, doff.data(), (C + 1ull) * 8, hipMemcpyDeviceToHost));
+    if (Jf) {
+        HIP_TRY(c, hipMemcpy(dk_out, dk.data(), Jf * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(fk_out, fk.data(), Jf * 8, hipMemcpyDeviceToHost));
+    }
+    *Jf_out = Jf;
+    *C_out = C;
+    return RDF_OK;
+}
+
+rdf_status rdf_test_group_build(rdf_ctx* c, const uint64_t* fk_host, uint64_t n, uint32_t V, uint64_t rbase, uint32_t gbase,
+                                uint64_t* G_out, uint64_t* goff_out, uint32_t* gcap_out, uint32_t* gmap_out,
+                                uint32_t* canaries_ok) {
+    if (!c) return RDF_ERR_ARG;
+    if (!canaries_ok || !G_out || !goff_out || !gmap_out || (n && (!fk_host || !gcap_out)))
+        return fail(c, RDF_ERR_ARG, "rdf_test_group_build: null argument");
+    *canaries_ok = 0;
+    *G_out = 0;
+    if (V < 1 || n >= (1ull << 32) || rbase >= (1ull << 32) || (u64)gbase + n >= (1ull << 32))
+        return fail(c, RDF_ERR_ARG, "rdf_test_group_build: V, n, rbase or gbase out of range");
+    for (u64 i = 0; i < n; ++i)
+        if ((fk_host[i] >> 32) >= V || (i && (fk_host[i] >> 32) < (fk_host[i - 1] >> 32)))
+            return fail(c, RDF_ERR_ARG, "rdf_test_group_build: the records are not sorted by join value or name one >= V");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const unsigned nt = (unsigned)((n + KT_TILE - 1) / KT_TILE);
+    TestArr fk, theads, tgbase, goff, gcap, gmap;
+    HIP_TRY(c, fk.make(8, n, 0, st));
+    HIP_TRY(c, theads.make(4, nt, 0, st));
+    HIP_TRY(c, tgbase.make(4, nt + 1ull, 0, st));
+    HIP_TRY(c, gcap.make(4, rbase + n, 0, st));
+    HIP_TRY(c, gmap.make(4, V, 0, st));
+    if (n) HIP_TRY(c, hipMemcpyAsync(fk.data(), fk_host, n * 8, hipMemcpyHostToDevice, st));
+    if (nt) hipLaunchKernelGGL(k_group_flags, dim3(nt), dim3(RDF_BLOCK), 0, st, (const u64*)fk.data(), n, (u32*)theads.data());
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        e = exclusive_scan_u32(c->ws, (const u32*)theads.data(), (u32*)tgbase.data(), nt, (u32*)tgbase.data() + nt, st);
+    u32 G = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&G, (u32*)tgbase.data() + nt, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    TRY(prim_status(c, e, "rdf_test_group_build (counting pass)"));
+    if (G > n) return fail(c, RDF_ERR_HIP, "rdf_test_group_build: more groups than records");
+    HIP_TRY(c, goff.make(8, (u64)gbase + G + 1, 0, st));
+    if (nt) {
+        if (rbase || gbase)
+            hipLaunchKernelGGL(k_group_build_at, dim3(nt), dim3(RDF_BLOCK), 0, st, (const u64*)fk.data(), n,
+                               (const u32*)tgbase.data(), rbase, gbase, (u64*)goff.data(), (u32*)gcap.data(), (u32*)gmap.data());
+        else
+            hipLaunchKernelGGL(k_group_build, dim3(nt), dim3(RDF_BLOCK), 0, st, (const u64*)fk.data(), n,
+                               (const u32*)tgbase.data(), (u64*)goff.data(), (u32*)gcap.data(), (u32*)gmap.data());
+    }
+    e = hipGetLastError();
+    const u64 end = rbase + n;  // the end of the last group: the caller's to write, as in the pipeline
+    HIP_TRY(c, hipMemcpyAsync((u64*)goff.data() + gbase + G, &end, 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    bool ok = true;
+    for (const TestArr* a : {&fk, &theads, &tgbase, &goff, &gcap, &gmap}) HIP_TRY(c, check_canaries(*a, &ok));
+    HIP_TRY(c, check_contents(fk, fk_host, n, &ok));      // the records are read only
+    HIP_TRY(c, check_contents(gcap, nullptr, rbase, &ok));  // nothing before the range's records ...
+    HIP_TRY(c, check_contents(goff, nullptr, gbase, &ok));  // ... or before its groups is written
+    *canaries_ok = ok ? 1 : 0;
+    TRY(prim_status(c, e, "rdf_test_group_build"));
+    HIP_TRY(c, hipMemcpy(goff_out, (u64*)goff.data() + gbase, (G + 1ull) * 8, hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(c, hipMemcpy(gcap_out, (u32*)gcap.data() + rbase, n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(gmap_out, gmap.data(), (u64)V * 4, hipMemcpyDeviceToHost));
+    *G_out = G;
+    return RDF_OK;
+}
+
 rdf_status rdf_test_paths(rdf_ctx* c, rdf_test_path_report* out) {
     if (!c || !out) return RDF_ERR_ARG;
     if (c->stage < 4) return fail(c, RDF_ERR_STATE, "no completed run");
