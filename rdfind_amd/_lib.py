@@ -127,7 +127,9 @@ class PathReport(ctypes.Structure):
                 ("n_light_survivors", ctypes.c_uint64),
                 ("light_npx", ctypes.c_uint32), ("packed_npx", ctypes.c_uint32), ("light_ordered", ctypes.c_uint32),
                 ("light_side", ctypes.c_uint32), ("light_two_pass", ctypes.c_uint32), ("sig_on", ctypes.c_uint32),
-                ("piv2_on", ctypes.c_uint32), ("k3_hist", ctypes.c_uint32)]
+                ("piv2_on", ctypes.c_uint32), ("k3_hist", ctypes.c_uint32),
+                ("hclassed", ctypes.c_uint32), ("n_class_chunks", ctypes.c_uint64), ("n_emit_tiles", ctypes.c_uint64),
+                ("max_class_list", ctypes.c_uint64), ("n_multi_seg_lists", ctypes.c_uint64)]
 
 
 class FcReport(ctypes.Structure):
@@ -914,13 +916,15 @@ class Context:
         n_packed_octets (k_light_packed), n_mseg_chunks (k_light_mseg_emit), n_multi_items (items of dependents with
         several chunks), n_light_survivors (pass B's input), light_npx / packed_npx (extra pivots checked), and the
         flags light_ordered, light_side, light_two_pass, sig_on, piv2_on, k3_hist (K3 handed the record sort its first
-        digit histogram)."""
+        digit histogram).  Of the mask classes, as the run left them on the device: hclassed (binary heavy-only
+        dependents read the class lists), n_class_chunks (k_class_eval work items), n_emit_tiles (k_class_emit tiles),
+        max_class_list (refs of the longest L'(m)) and n_multi_seg_lists (lists longer than one emission segment)."""
         r = PathReport()
         self._check(self._test_fn("rdf_test_paths")(self.ptr, ctypes.byref(r)), "rdf_test_paths")
         d = _struct_dict(r)
         d["k1_form"], d["k2_form"], d["k3_form"] = K1_FORMS[r.k1_form], K2_FORMS[r.k2_form], K3_FORMS[r.k3_form]
         for name in ("dense_on", "light_stage", "light_hiocc", "light_ordered", "light_side", "light_two_pass", "sig_on",
-                     "piv2_on", "k3_hist"):
+                     "piv2_on", "k3_hist", "hclassed"):
             d[name] = bool(d[name])
         return d
 

@@ -125,6 +125,14 @@ typedef struct rdf_test_path_report {
     uint32_t sig_on;               /* the run computed light-group signatures */
     uint32_t piv2_on;              /* ... and second pivots */
     uint32_t k3_hist;              /* K3 counted the record sort's first digit: the sort's first pass read K3's regions */
+    /* The mask classes of the last discovery, read from what the run left on the device when rdf_test_paths is called
+     * (the run itself does no more for them).  The chunk and list fields are those of a single-GPU run; a rank of a
+     * sharded run among several reports 0. */
+    uint32_t hclassed;             /* the binary heavy-only dependents took their refs from the class lists */
+    uint64_t n_class_chunks;       /* k_class_eval work items: chunks of 64 members of the classes' pivot groups */
+    uint64_t n_emit_tiles;         /* k_class_emit tiles of the class part (member tiles x list segments) */
+    uint64_t max_class_list;       /* refs of the longest class list L'(m) */
+    uint64_t n_multi_seg_lists;    /* class lists longer than one emission segment (CLS_LS refs) */
 } rdf_test_path_report;
 
 rdf_status rdf_test_paths(rdf_ctx* ctx, rdf_test_path_report* out);

@@ -436,6 +436,29 @@ rdf_status rdf_test_paths(rdf_ctx* c, rdf_test_path_report* out) {
     r.sig_on = c->sig_on ? 1 : 0;
     r.piv2_on = c->piv2_on ? 1 : 0;
     r.k3_hist = c->k3_hist ? 1 : 0;
+    r.hclassed = c->hclassed ? 1 : 0;
+    r.n_emit_tiles = c->pend_NT;
+    // the class lists as the run left them: class m's is lists[lwoff[cchoff[m]], lwoff[cchoff[m + 1]]).  n_classes and
+    // pend_NT belong to the last discovery because every discovery path sets both (d_classes_single / the sharded class
+    // phases, and d_emit_rest), also to 0; stage >= 4 (above) says that such a run completed and rdf_release_scratch has
+    // not freed its buffers since.  The capacities are checked so that a stale count can never read past a buffer.
+    const u64 ncls = c->nranks == 1 ? c->n_classes : 0;
+    if (ncls && (u64)c->cchoff.cap >= (ncls + 1) * 8) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        std::vector<u64> ch(ncls + 1);
+        HIP_TRY(c, hipMemcpy(ch.data(), c->cchoff.p, (ncls + 1) * 8, hipMemcpyDeviceToHost));
+        const u64 WC = ch[ncls];
+        if ((u64)c->lwoff.cap < (WC + 1) * 8) return fail(c, RDF_ERR_STATE, "rdf_test_paths: the class lists are gone");
+        std::vector<u64> lw(WC + 1);
+        HIP_TRY(c, hipMemcpy(lw.data(), c->lwoff.p, (WC + 1) * 8, hipMemcpyDeviceToHost));
+        r.n_class_chunks = WC;
+        for (u64 m = 0; m < ncls; ++m) {
+            const u64 len = lw[ch[m + 1]] - lw[ch[m]];
+            r.max_class_list = std::max<u64>(r.max_class_list, len);
+            r.n_multi_seg_lists += len > CLS_LS;
+        }
+    }
     *out = r;
     return RDF_OK;
 }
