@@ -61,7 +61,7 @@ RDF_NT_TABS = 1
 TEST_SYMBOLS = ("rdf_test_scan", "rdf_test_scan_batch", "rdf_test_radix", "rdf_test_radix_passes",
                 "rdf_test_radix_segments", "rdf_test_paths", "rdf_test_rewrite_form", "rdf_test_cind_stats_times",
                 "rdf_test_fc_trace", "rdf_test_fc_report", "rdf_test_copy_frequent_unary", "rdf_test_unary_lookup",
-                "rdf_test_record_tile", "rdf_test_keep_records", "rdf_test_group_build")
+                "rdf_test_record_tile", "rdf_test_keep_records", "rdf_test_group_build", "rdf_test_shard_report")
 REWRITE_FORMS = {0: None, 1: "lds", 2: "global"}
 SCAN_U32_U32, SCAN_U32_U64, SCAN_U64_U64 = range(3)
 SCAN_DTYPES = {SCAN_U32_U32: (np.uint32, np.uint32), SCAN_U32_U64: (np.uint32, np.uint64),
@@ -138,6 +138,17 @@ class FcReport(ctypes.Structure):
                 ("k2_form", ctypes.c_uint32), ("k2_bits", ctypes.c_uint32), ("k2_sub", ctypes.c_uint32),
                 ("k1_buckets", ctypes.c_uint64), ("k1_slices", ctypes.c_uint64), ("k1_multi", ctypes.c_uint64),
                 ("k2_buckets", ctypes.c_uint64), ("k2_multi", ctypes.c_uint64), ("k2_spill", ctypes.c_uint64)]
+
+
+class ShardReport(ctypes.Structure):
+    """rdf_test_shard_report_t (rdfind_amd/csrc/test_abi.h)."""
+    _fields_ = ([("rank", ctypes.c_uint32), ("nranks", ctypes.c_uint32)]
+                + [(k, ctypes.c_uint64) for k in (
+                    "holder_survivors", "routed_words", "reports_sent", "verify_sent", "reports_received",
+                    "verify_received", "verify_kept", "owner_reports", "owner_kept", "unary_own", "binary_own",
+                    "unary_gathered", "n_classes", "n_class_members", "n_class_items", "n_list_entries", "hot_entries",
+                    "heavy_base", "heavy_columns")]
+                + [("have_max_verify", ctypes.c_uint32), ("max_verify_per_dep", ctypes.c_uint64)])
 
 
 class ResultLayout(ctypes.Structure):
@@ -327,6 +338,7 @@ def load():
         "rdf_test_cind_stats_times": (i32, [P, ctypes.POINTER(ctypes.c_float)]),
         "rdf_test_fc_trace": (i32, [P, ctypes.c_int]),
         "rdf_test_fc_report": (i32, [P, ctypes.POINTER(FcReport)]),
+        "rdf_test_shard_report": (i32, [P, ctypes.POINTER(ShardReport)]),
         "rdf_test_copy_frequent_unary": (i32, [P, P, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "rdf_test_unary_lookup": (i32, [P, P, u64, P, P, ctypes.POINTER(u32)]),
         "rdf_test_record_tile": (ctypes.c_int, []),
@@ -926,6 +938,19 @@ class Context:
         for name in ("dense_on", "light_stage", "light_hiocc", "light_ordered", "light_side", "light_two_pass", "sig_on",
                      "piv2_on", "k3_hist", "hclassed"):
             d[name] = bool(d[name])
+        return d
+
+    def test_shard_report(self) -> dict:
+        """What the exchange of the last completed sharded run did on this rank (rdf_test_shard_report): the holder's
+        survivors, the words routed (reports and verify words), the reports and verify pairs received, the verify pairs
+        kept, the owner's reports and need-complete pairs, the unary and binary pairs, the class counts, the hot table's
+        entries, the heavy bit base and columns; max_verify_per_dep (None when the verify offsets are gone) is read
+        from the device when this is called."""
+        r = ShardReport()
+        self._check(self._test_fn("rdf_test_shard_report")(self.ptr, ctypes.byref(r)), "rdf_test_shard_report")
+        d = _struct_dict(r)
+        if not d.pop("have_max_verify"):
+            d["max_verify_per_dep"] = None
         return d
 
     def test_fc_trace(self, on: bool = True):

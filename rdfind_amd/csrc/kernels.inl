@@ -1240,6 +1240,24 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_group_size_hist(const u64* __rest
     if (lh[threadIdx.x]) atomicAdd(&hist[threadIdx.x], lh[threadIdx.x]);
 }
 
+// groups of size bucket `bucket` with fewer than min_size members: the part of the bucket a heavy minimum inside it
+// keeps light (sharded runs whose RDFIND_HEAVY_MIN does not start a bucket: the histogram alone cannot tell them from
+// the bucket's columns).  One atomic per block.
+__global__ __launch_bounds__(RDF_BLOCK) void k_count_below_min(const u64* __restrict__ goff, u64 G, int bucket, u64 min_size,
+                                                               u32* out) {
+    __shared__ u32 n;
+    if (threadIdx.x == 0) n = 0;
+    __syncthreads();
+    u32 mine = 0;
+    for (u64 g = (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; g < G; g += (u64)gridDim.x * RDF_BLOCK) {
+        const u64 sz = goff[g + 1] - goff[g];
+        mine += (size_bucket(sz) == bucket && sz < min_size) ? 1u : 0u;
+    }
+    if (mine) atomicAdd(&n, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && n) atomicAdd(out, n);
+}
+
 // heavy threshold on the device (single GPU: no host round trip between the histogram and the selection): the
 // smallest size bucket such that the groups in it and above number at most HMAX, its smallest size, at least min_size;
 // 0 = no heavy groups.  The same rule as the host's heavy_threshold (rdfind_hip.hip), which sharded runs use on the

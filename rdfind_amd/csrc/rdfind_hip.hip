@@ -307,6 +307,11 @@ struct rdf_ctx : CtxBuffers {
     // on, the stage also reads its slice lists back (fc_trace_slices)
     bool fc_trace = false;
     rdf_test_fc_report_t fcrep = {};
+    // rdf_test_shard_report (test_abi.h): host numbers of the last sharded run's exchange, noted by its phases;
+    // shrep_done: phase 8 completed; shrep_vC: the C of the vcoff sh_phase15 left (~0: vcoff holds something else)
+    rdf_test_shard_report_t shrep = {};
+    bool shrep_done = false;
+    u64 shrep_vC = ~0ull;
     // the last group build's K3 handed the record sort its first digit histogram (RDFIND_EMIT_HIST)
     bool k3_hist = false;
     // what the light launches of the last discovery were given (d_light_kernels; sums over its pages, ranges and
@@ -2861,11 +2866,14 @@ static u64 heavy_threshold(const rdf_ctx* c, const u32* hist) {
     return tb >= 0 ? std::max<u64>(bucket_min_size(tb), c->sw.heavy_min) : 0;
 }
 
-// groups of a histogram at or above the threshold (exact: a power-of-two heavy_min starts a bucket)
-static u64 heavy_count(const u32* hist, u64 thr) {
+// groups of a histogram at or above the threshold.  below_min: the groups of the bucket of RDFIND_HEAVY_MIN that are
+// smaller than it (k_count_below_min; 0 where the minimum starts its bucket, as every power of two does): when the
+// minimum is the threshold they share its bucket with the columns and are none.
+static u64 heavy_count(const u32* hist, u64 thr, u64 heavy_min = 0, u64 below_min = 0) {
     if (!thr) return 0;
     u64 n = 0;
     for (int b = size_bucket(thr); b < 256; ++b) n += hist[b];
+    if (thr == heavy_min) n -= std::min(n, below_min);
     return n;
 }
 
@@ -2977,6 +2985,7 @@ rdf_status rdf_build_capture_groups(rdf_ctx* c, const char* projection, rdf_grou
     TRY(parse_projection(c, projection, &proj));
     c->rank = 0;
     c->nranks = 1;
+    c->shrep_done = false;
     c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;
     c->n_group_ranges = 1;
     if (c->sw.group_range_records || 9 * c->n >= (1ull << 32)) {
@@ -3479,6 +3488,7 @@ static rdf_status d_light_two_pass(rdf_ctx* c, const CindView& v, u64 WI, u64 WL
     tbegin(c, RDF_T_LIGHT);
     ENSURE(c, flags, std::max<u64>(WL, 1) * 4);
     ENSURE(c, vcoff, (std::max<u64>(WL, C) + 1ull) * 8);  // tagged octet offsets first, then pass B's dependent offsets
+    c->shrep_vC = ~0ull;
     if (WL)
         hipLaunchKernelGGL(k_tag_octets, dim3(grid_for(WL, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, c->epairs_tmp.as<u64>(),
                            c->lslot.as<u32>(), WL, c->flags.as<u32>());
@@ -4711,9 +4721,22 @@ static rdf_status sh_phase1(rdf_ctx* c, rdf_exchange* req) {
     c->spare_x = false;  // the exchange buffers carry the collectives again
     if (c->ar_on) TRY(g_ar_refs(c));
     TRY(g_size_hist(c, c->h_hist_local));
+    // a heavy minimum inside a size bucket: the bucket's groups below it travel in the high half of its word, so that
+    // every rank counts every rank's columns exactly (bit bases without gaps, n_heavy_groups as on one GPU)
+    const u64 hm = c->sw.heavy_min;
+    const int bm = size_bucket(hm);
+    u32 below = 0;
+    if (c->G && hm > bucket_min_size(bm)) {
+        u32* d_below = c->hist.as<u32>() + 260;  // (256: the column counter, 258..259: the device threshold)
+        HIP_TRY(c, hipMemsetAsync(d_below, 0, 4, c->stream));
+        hipLaunchKernelGGL(k_count_below_min, dim3(grid_for(c->G, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, c->stream,
+                           c->goff.as<u64>(), c->G, bm, hm, d_below);
+        TRY(read_u32(c, d_below, &below));
+    }
     ENSURE(c, xsend, 256 * 8);
     std::vector<u64> w(256);
     for (int i = 0; i < 256; ++i) w[i] = c->h_hist_local[i];
+    w[bm] |= (u64)below << 32;
     HIP_TRY(c, ctx_copy(c, c->xsend.p, w.data(), 256 * 8, hipMemcpyHostToDevice));
     return x_request(c, req, RDF_X_ALLGATHERV_U64, c->xsend.p, 256, 2);
 }
@@ -4727,15 +4750,22 @@ static rdf_status sh_phase2(rdf_ctx* c, rdf_exchange* req) {
     for (u32 r = 0; r < R; ++r)
         for (int b = 0; b < 256; ++b) gh[b] += (u32)all[256ull * r + b];
     const u64 thr = heavy_threshold(c, gh);
+    const u64 hm = c->sw.heavy_min;
+    const int bm = size_bucket(hm);
     u32 base = 0;
-    for (u32 r = 0; r < c->rank; ++r) {
+    u64 total = 0;
+    for (u32 r = 0; r < R; ++r) {
         u32 lh[256];
         for (int b = 0; b < 256; ++b) lh[b] = (u32)all[256ull * r + b];
-        base += (u32)heavy_count(lh, thr);
+        const u64 cols = heavy_count(lh, thr, hm, all[256ull * r + bm] >> 32);
+        if (r < c->rank) base += (u32)cols;
+        total += cols;
     }
     TRY(g_heavy_binary(c, thr, base));
     TRY(g_finish(c, nullptr));
-    c->gstats.n_heavy_groups = heavy_count(gh, thr);
+    c->gstats.n_heavy_groups = total;
+    c->shrep.heavy_base = base;
+    c->shrep.heavy_columns = c->nheavy;  // (read back by g_heavy_binary: the columns this rank numbered)
     ENSURE(c, xsend, std::max<u64>(c->C, 1) * 8);
     if (c->C)
         hipLaunchKernelGGL(k_extract_hmask, dim3(grid_for(c->C, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, c->stream,
@@ -4829,6 +4859,9 @@ static rdf_status sh_phase5(rdf_ctx* c, rdf_exchange* req) {
     std::vector<u64> bounds(R + 1);
     HIP_TRY(c, hipMemcpyAsync(bounds.data(), c->obounds.p, (R + 1) * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
+    c->shrep.holder_survivors = c->shrep.reports_sent = E;
+    c->shrep.routed_words = T;
+    c->shrep.verify_sent = T - E;
     TRY(x_request(c, req, RDF_X_ALLTOALLV_U64, c->cpairs.p, T, 15));
     for (u32 r = 0; r < R; ++r) req->send_counts[r] = bounds[r + 1] - bounds[r];
     return RDF_OK;
@@ -4919,6 +4952,10 @@ static rdf_status sh_phase15(rdf_ctx* c, rdf_exchange* req) {
     c->light_entries = le;
     TRY(d_light(c, v, WI, WL, WP, &E, c->vpiv.as<u32>()));
     c->n_light_chunks += WL;
+    c->shrep.reports_received = nh;
+    c->shrep.verify_received = nv;
+    c->shrep.verify_kept = E;
+    c->shrep_vC = C;
     return sh_to_owners(c, req, E, 6);
 }
 
@@ -4959,6 +4996,10 @@ static rdf_status sh_phase6(rdf_ctx* c, rdf_exchange* req) {
     u64 Eu = 0;
     TRY(read_u64(c, c->obounds.as<u64>(), &Eu));
     c->sh_Eb = E - Eu;
+    c->shrep.owner_reports = n;
+    c->shrep.owner_kept = E;
+    c->shrep.unary_own = Eu;
+    c->shrep.binary_own = E - Eu;
     ENSURE(c, ebown, std::max<u64>(E - Eu, 1) * 8);
     if (E > Eu) HIP_TRY(c, hipMemcpyAsync(c->ebown.p, c->xsend.as<u64>() + Eu, (E - Eu) * 8, hipMemcpyDeviceToDevice, st));
     tend(c, RDF_T_ESORT);
@@ -5081,6 +5122,11 @@ static rdf_status sh_phase7(rdf_ctx* c, rdf_exchange* req) {
     HIP_TRY(c, exclusive_scan_u32_u64(c->ws, c->ccnt.as<u32>(), c->lwoff.as<u64>(), WC, c->lwoff.as<u64>() + WC, st));
     u64 LT = 0;
     TRY(read_u64(c, c->lwoff.as<u64>() + WC, &LT));
+    c->shrep.unary_gathered = Eu;
+    c->shrep.n_classes = ncls;
+    c->shrep.n_class_members = nmem;
+    c->shrep.n_class_items = WC;
+    c->shrep.n_list_entries = LT;
     ENSURE(c, xsend, std::max<u64>(LT, 1) * 8);
     if (WC)
         hipLaunchKernelGGL(k_class_write, dim3(vgrid(wave_blocks(WC))),
@@ -5121,6 +5167,8 @@ static rdf_status sh_phase8(rdf_ctx* c, rdf_exchange* req) {
     memset(req, 0, sizeof(*req));
     req->op = RDF_X_DONE;
     c->sh_phase = 9;
+    c->shrep.hot_entries = c->nranks > 1 ? c->hot_n : 0;
+    c->shrep_done = true;
     mem_report(c);
     return RDF_OK;
 }
@@ -5399,6 +5447,11 @@ rdf_status rdf_shard_begin(rdf_ctx* c, uint32_t rank, uint32_t nranks, uint32_t 
     c->sh_proj = proj;
     c->sh_flags = flags;
     c->sh_phase = 10;
+    c->shrep = {};
+    c->shrep.rank = rank;
+    c->shrep.nranks = nranks;
+    c->shrep_done = false;
+    c->shrep_vC = ~0ull;
     c->x_imported = true;
     c->spare_x = false;  // (a run that failed between phases 14 and 1 left them marked)
     c->stage = std::min(c->stage, 1);

@@ -137,6 +137,38 @@ typedef struct rdf_test_path_report {
 
 rdf_status rdf_test_paths(rdf_ctx* ctx, rdf_test_path_report* out);
 
+/* What the exchange of the last completed sharded run (rdf_shard_begin .. RDF_X_DONE) did on this rank
+ * (RDF_ERR_STATE without one, or after a later run of another kind).  Every field but the last is a number the phases
+ * hold on the host anyway: a run launches, copies and waits exactly as it did.  max_verify_per_dep is computed when the
+ * call is made, from the verify offsets sh_phase15 left on the device (have_max_verify = 0, and the field 0, when they
+ * are gone). */
+typedef struct rdf_test_shard_report_t {
+    uint32_t rank, nranks;
+    uint64_t holder_survivors;   /* pairs this rank's holder pass kept (phase 5) */
+    uint64_t routed_words;       /* words it routed: reports_sent + verify_sent */
+    uint64_t reports_sent;       /* ... one report per survivor to the dependent's owner */
+    uint64_t verify_sent;        /* ... and one verify word per other rank with a light group of the dependent */
+    uint64_t reports_received;   /* holders' reports received as an owner (phase 15) */
+    uint64_t verify_received;    /* verify pairs received (phase 15) */
+    uint64_t verify_kept;        /* ... of which this rank's verify pass kept */
+    uint64_t owner_reports;      /* phase 6: holders' and verifiers' reports this owner counted */
+    uint64_t owner_kept;         /* ... distinct pairs reported by every rank with a light group (need-complete) */
+    uint64_t unary_own;          /* ... of those, pairs of unary dependents (sent to every rank) */
+    uint64_t binary_own;         /* ... and pairs of binary dependents (kept here) */
+    uint64_t unary_gathered;     /* unary dependents' pairs of all ranks (phase 7) */
+    uint64_t n_classes;          /* mask classes (the same on every rank) */
+    uint64_t n_class_members;    /* class members this rank owns */
+    uint64_t n_class_items;      /* class work items (chunks of 64 pivot members) of the classes pivoted here */
+    uint64_t n_list_entries;     /* class list entries this rank contributed to the all-gather */
+    uint64_t hot_entries;        /* entries of the hot owner table */
+    uint64_t heavy_base;         /* this rank's first heavy bit */
+    uint64_t heavy_columns;      /* heavy columns of this rank's join shard */
+    uint32_t have_max_verify;
+    uint64_t max_verify_per_dep; /* the most verify pairs received for one dependent */
+} rdf_test_shard_report_t;
+
+rdf_status rdf_test_shard_report(rdf_ctx* ctx, rdf_test_shard_report_t* out);
+
 /* Frequent-condition counting (K1 / K2, counts.inl) on its own: which branches the last rdf_frequent_conditions took,
  * and the frequent unary set it left on the device.  All four calls need only that stage (RDF_ERR_STATE before it and
  * after rdf_release_scratch), not a whole run.

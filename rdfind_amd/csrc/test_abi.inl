@@ -463,6 +463,26 @@ rdf_status rdf_test_paths(rdf_ctx* c, rdf_test_path_report* out) {
     return RDF_OK;
 }
 
+rdf_status rdf_test_shard_report(rdf_ctx* c, rdf_test_shard_report_t* out) {
+    if (!c || !out) return RDF_ERR_ARG;
+    if (!c->shrep_done || c->sh_phase != 9 || c->stage < 4)
+        return fail(c, RDF_ERR_STATE, "rdf_test_shard_report: no completed sharded run");
+    rdf_test_shard_report_t r = c->shrep;
+    // the verify offsets as sh_phase15 left them: vcoff[0, C] of that run's C (shrep_vC says nothing has written the
+    // buffer since; the capacity is checked so that a released buffer is never read)
+    const u64 C = c->shrep_vC;
+    if (C != ~0ull && C == c->C && (u64)c->vcoff.cap >= (C + 1) * 8) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        std::vector<u64> off(C + 1);
+        HIP_TRY(c, hipMemcpy(off.data(), c->vcoff.p, (C + 1) * 8, hipMemcpyDeviceToHost));
+        for (u64 d = 0; d < C; ++d) r.max_verify_per_dep = std::max<u64>(r.max_verify_per_dep, off[d + 1] - off[d]);
+        r.have_max_verify = 1;
+    }
+    *out = r;
+    return RDF_OK;
+}
+
 rdf_status rdf_test_fc_trace(rdf_ctx* c, int on) {
     if (!c) return RDF_ERR_ARG;
     c->fc_trace = on != 0;

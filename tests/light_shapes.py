@@ -46,6 +46,13 @@ shapes that must prove "no k_light item" have no supersets of ``D``: their true 
 near-misses share one extra subject (a second extra would be a small pivot group).  A dependent has at most HMAX heavy
 groups, so "at most 16 light" means at most 80 groups: the second rule's edge is m = 80 / 81 (64 ballast + 16 / 17
 light groups), and its 512-group bound cannot be reached by any input.
+
+Shared objects.  With fresh objects no binary condition is frequent, so the minimality rules of the explicit path never
+see a near-miss.  ``shared_objects=True`` gives every triple of set ``k`` the one object ``O_k`` instead: ``s[p=P_k]``,
+``s[o=O_k]`` and ``s[p=P_k,o=O_k]`` then share the join set ``S_k`` (three twins per set with equal group lists), every
+inclusion and every near-miss exists in nine capture combinations, and the rules remove about two thirds of the raw
+rows.  Subjects, positions and misses are those of the plain form, so the position model above still holds (private
+predicates keep their fresh objects).  The expected rows of this form come from the oracles alone.
 """
 from __future__ import annotations
 
@@ -77,6 +84,13 @@ class Shape:
     o: np.ndarray = field(default=None, repr=False)
     num_terms: int = 0
     min_support: int = 2
+    n_pred: int = 0  # predicates: the sets' and the private ones
+    shared_objects: bool = False
+
+    def obj(self, k: int) -> int:
+        """Term id of O_k, the one object of set k in the shared-object form."""
+        assert self.shared_objects
+        return self.n_subjects + self.n_pred + k
 
     @property
     def n(self):
@@ -173,12 +187,13 @@ def miss_positions(m: int, n_near: int, rng, avoid=()) -> list:
 
 
 def make(name: str, m: int, n_true: int, n_near: int, *, n_sub: int = 0, ballast: bool = False, one_extra: bool = False,
-         n_other: int = 3, private_from: int = -1, seed: int = 1) -> Shape:
+         n_other: int = 3, private_from: int = -1, seed: int = 1, shared_objects: bool = False) -> Shape:
     """Build a shape.  one_extra: every near-miss adds the same single extra subject (the packed-edge shapes).  One
     near-miss is repeated as an identical set (equal group lists for the dedup classes).  private_from >= 0: every
     subject of D from that position on also has a predicate of its own (one triple: an infrequent condition, so
     projection s sees nothing of it); under projection spo it keeps the p[s=x] captures of the subjects of D, which
-    otherwise all have the same predicates, from including each other (m^2 rows)."""
+    otherwise all have the same predicates, from including each other (m^2 rows).  shared_objects: one object per set
+    instead of one per triple (the module's docstring)."""
     rng = np.random.default_rng(seed)
     D = np.arange(m, dtype=np.int64)
     bal = np.zeros(0, np.int64)
@@ -245,10 +260,17 @@ def make(name: str, m: int, n_true: int, n_near: int, *, n_sub: int = 0, ballast
     sh.s = np.concatenate(sets + [priv]).astype(np.uint32)
     sh.p = np.concatenate([np.repeat(n_subjects + np.arange(len(sets)), sizes),
                            n_subjects + len(sets) + np.arange(len(priv))]).astype(np.uint32)
-    sh.o = (n_subjects + n_pred + np.arange(sh.s.shape[0])).astype(np.uint32)
+    if shared_objects:  # O_k per set; the private predicates' triples keep objects of their own
+        sh.o = (n_subjects + n_pred + np.concatenate([np.repeat(np.arange(len(sets)), sizes),
+                                                      len(sets) + np.arange(len(priv))])).astype(np.uint32)
+        n_obj = len(sets) + len(priv)
+    else:
+        sh.o = (n_subjects + n_pred + np.arange(sh.s.shape[0])).astype(np.uint32)
+        n_obj = sh.s.shape[0]
     perm = rng.permutation(sh.s.shape[0])  # triples in no particular order
     sh.s, sh.p, sh.o = sh.s[perm], sh.p[perm], sh.o[perm]
-    sh.num_terms = int(n_subjects + n_pred + sh.s.shape[0])
+    sh.num_terms = int(n_subjects + n_pred + n_obj)
+    sh.n_pred, sh.shared_objects = n_pred, bool(shared_objects)
     assert min(len(x) for x in sets) >= 2 and np.bincount(np.concatenate(sets), minlength=n_subjects).min() >= 2
     return sh
 
@@ -276,16 +298,18 @@ BALLAST_FORMS = ("small300", "cand63", "cand64", "cand65", "cand129", "seg2", "s
 _CACHE: dict = {}
 
 
-def shape(name: str, ballast: bool = False) -> Shape:
+def shape(name: str, ballast: bool = False, shared_objects: bool = False) -> Shape:
     """The named shape, built once per process.  ballast: its form for the default heavy setting (64 columns taken by
     ballast subjects); without: the form for RDFIND_HEAVY_MIN=NO_HEAVY.  The pack80h / pack81h shapes always carry
-    ballast (they run under RDFIND_HEAVY_MIN=2)."""
-    key = (name, bool(ballast))
+    ballast (they run under RDFIND_HEAVY_MIN=2).  shared_objects: one object per set (name suffix "+o"): the same sets,
+    subjects and seed as the plain form."""
+    key = (name, bool(ballast), bool(shared_objects))
     if key not in _CACHE:
         kw = dict(SPECS[name][0])
         if ballast:
             kw["ballast"] = True
-        _CACHE[key] = make(name + ("+b" if ballast else ""), seed=len(name) * 131 + kw["m"], **kw)
+        _CACHE[key] = make(name + ("+b" if ballast else "") + ("+o" if shared_objects else ""),
+                           seed=len(name) * 131 + kw["m"], shared_objects=shared_objects, **kw)
     return _CACHE[key]
 
 

@@ -10,8 +10,10 @@
 * ``dataset_npz(cfg, scale)``: the same input saved once as .npy files, for child processes that must start fresh
   (switches read when the context is created) without regenerating it;
 * ``shape_rows(sh, ...)`` / ``assert_shape_rows(ctx, sh, ...)``: the oracle's sorted packed rows of a near-miss shape
-  (tests/light_shapes.py) or a heavy / class shape (tests/heavy_shapes.py) per (shape, mode, projection), cached for the
-  session, and the row-exact comparison with them.
+  (tests/light_shapes.py, either form) or a heavy / class shape (tests/heavy_shapes.py) per (shape, form, mode,
+  projection), cached for the session, and the row-exact comparison with them;
+* ``expected_checksum(keys, supports)``: the library's order-independent result checksum of expected rows;
+* ``ars_expected(sh, ...)``: the rules and the CIND set of a shape with association rules on (Python oracle), cached.
 """
 from __future__ import annotations
 
@@ -122,7 +124,7 @@ def shape_rows(sh, strategy: int = 1, clean: bool = True, projection: str = "s")
     Mode (1, False), the exact-candidate S2L raw output, has only the Python restatement as its oracle (as in
     tests/test_gpu.py expected_set); its rows are turned into capture ids with the C oracle's binary-key table (both
     index the sorted frequent binary keys)."""
-    key = (sh.name, strategy, bool(clean), projection)
+    key = (sh.name, bool(getattr(sh, "shared_objects", False)), strategy, bool(clean), projection)
     if key in _SHAPE_ROWS:
         return _SHAPE_ROWS[key]
     if strategy == 1 and not clean and getattr(sh, "algebra_raw_s2l", False):
@@ -159,6 +161,22 @@ def shape_rows(sh, strategy: int = 1, clean: bool = True, projection: str = "s")
     return _SHAPE_ROWS[key]
 
 
+def shared_captures(sh):
+    """External capture ids (projection s) of the three captures every set k of a shared-object light shape has:
+    int64 [n_sets, 3] = s[p=P_k], s[o=O_k], s[p=P_k,o=O_k] (the binary id indexes the C oracle's sorted frequent binary
+    keys, as on the device)."""
+    from rdfind_amd import codes
+    _, bkeys, _ = C.run(sh.s, sh.p, sh.o, sh.num_terms, sh.min_support, 0, False, "s")
+    V = sh.num_terms
+    out = np.zeros((len(sh.sets), 3), np.int64)
+    for k in range(len(sh.sets)):
+        key = (codes.BINARY_TYPE_INDEX[14] << 62) | (sh.pred(k) << 31) | sh.obj(k)
+        j = int(np.searchsorted(bkeys, np.uint64(key)))
+        assert j < len(bkeys) and int(bkeys[j]) == key, (sh.name, k)
+        out[k] = (codes.UNARY_TYPE_INDEX[10] * V + sh.pred(k), codes.UNARY_TYPE_INDEX[12] * V + sh.obj(k), 6 * V + j)
+    return out
+
+
 def device_rows(ctx):
     """(sorted dep << 32 | ref keys, supports) of the context's current result from its id-records
     (rdf_copy_result_raw: refs, run table, capture ids, supports), decoded here.  Every ref and dependent id is checked
@@ -180,15 +198,50 @@ def device_rows(ctx):
 
 
 def assert_shape_rows(ctx, sh, strategy: int = 1, clean: bool = True, projection: str = "s", what=None):
-    """Every row of the context's current result equals the oracle's rows of the shape.  A heavy / class shape is
-    decoded by device_rows, whose ids are checked before use."""
+    """Every row of the context's current result equals the oracle's rows of the shape.  A heavy / class shape and a
+    shared-object light shape are decoded by device_rows, whose ids are checked before use."""
     ek, es = shape_rows(sh, strategy, clean, projection)
-    gk, gs = device_rows(ctx) if hasattr(sh, "heavy_min") else packed(ctx.copy_cinds())
+    checked = hasattr(sh, "heavy_min") or getattr(sh, "shared_objects", False)
+    gk, gs = device_rows(ctx) if checked else packed(ctx.copy_cinds())
     assert gk.shape[0] == ek.shape[0], (sh.name, strategy, clean, projection, what, gk.shape[0], ek.shape[0],
                                         _first_diff(gk, ek))
     bad = np.nonzero(gk != ek)[0]
     assert bad.size == 0, (sh.name, strategy, clean, projection, what, _first_diff(gk, ek))
     np.testing.assert_array_equal(gs, es)
+
+
+_ARS: dict = {}
+
+
+def ars_expected(sh, strategy: int, clean: bool):
+    """(sorted rules, CIND set) of a shape with --use-ars under projection spo: the Python oracle as
+    tests/test_gpu_ars.py states it (rules as (antecedent code, consequent code, values, count)); cached per session."""
+    key = (sh.name, strategy, bool(clean))
+    if key not in _ARS:
+        from oracle import rdfind_oracle as R
+        from tests.test_gpu_ars import CODE, expected
+        tr = list(zip(sh.s.tolist(), sh.p.tolist(), sh.o.tolist()))
+        if ("rules", sh.name) not in _ARS:
+            uf = R.frequent_unary_conditions(tr, sh.min_support)
+            bf = R.frequent_binary_conditions(tr, uf, sh.min_support)
+            _ARS[("rules", sh.name)] = sorted((CODE[ta], CODE[tc], va, vc, n) for ta, tc, va, vc, n in R.association_rules(uf, bf))
+        _ARS[key] = (_ARS[("rules", sh.name)], expected(tr, sh.min_support, strategy, clean))
+    return _ARS[key]
+
+
+_M64 = (1 << 64) - 1
+
+
+def expected_checksum(keys, supports) -> int:
+    """rdf_cind_checksum of the rows (sorted or not): the sum mod 2^64 of mix64(((dep << 32) | ref) + support * phi)
+    over external capture ids (tests/test_gpu_full.py states it; mix64 = the murmur3 finaliser of common.hpp)."""
+    x = keys.astype(np.uint64) + supports.astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)  # wraps mod 2^64
+    x ^= x >> np.uint64(33)
+    x *= np.uint64(0xFF51AFD7ED558CCD)
+    x ^= x >> np.uint64(33)
+    x *= np.uint64(0xC4CEB9FE1A85EC53)
+    x ^= x >> np.uint64(33)
+    return int(np.add.reduce(x, dtype=np.uint64)) & _M64 if x.size else 0
 
 
 def _first_diff(gk, ek):

@@ -230,6 +230,96 @@ def test_k3_count_and_write_form_random(monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the shared-object form (tests/light_shapes.py): one object per set, so every set has three captures with equal group
+# lists, frequent binary conditions exist and the minimality rules of the explicit path see the near-misses
+
+SHARED_FORMS = [("pack32", False), ("pack33", False), ("small300", False), ("cand64", False), ("cand65", False),
+                ("cand65", True), ("small300", True)]
+ALL_MODES = MODES + [(1, False)]
+
+
+DUP_MIN = 256  # switches.hpp RDFIND_DUP_MIN: the shortest group list that looks for an equal one by default
+
+
+def check_shared_paths(t, sh, name, sw, strategy, what):
+    """Every dependent has two twins with equal group lists.  With the dedup classes on for every list (the switch set
+    dedup_all) members must be found; by default the classes are looked for only where the light pass stages its rows
+    and only among lists of at least DUP_MIN groups (d_light_dedup), so the report says 0 wherever that rules them out."""
+    if strategy != 1:
+        assert t["n_dedup_members"] == 0, what
+    elif sw == "dedup_all" or (t["light_stage"] and sh.m >= DUP_MIN):
+        assert t["n_dedup_members"] > 0, what
+    elif not t["light_stage"] or len(max(sh.sets, key=len)) < DUP_MIN:
+        assert t["n_dedup_members"] == 0, what
+    if L.shape_class(name) == "packed":
+        assert t["n_packed_octets"] > 0, what
+    else:
+        assert t["n_light_items"] > 0, what
+
+
+@pytest.mark.parametrize("sw", ["defaults", "dedup_all"])
+@pytest.mark.parametrize("name,ballast", SHARED_FORMS, ids=[n + ("+b" if b else "") + "+o" for n, b in SHARED_FORMS])
+def test_shared_objects_four_modes(monkeypatch, name, ballast, sw):
+    """Row-exact in all four modes under projection s (rows decoded by parity.device_rows, ids checked first): the
+    explicit rules (k_rules_explicit -> rule_keep -> member, k_rules_mark) on inputs full of near-misses, in the default
+    setting and with the dedup classes on for every group list."""
+    sh = L.shape(name, ballast, shared_objects=True)
+    g = context(monkeypatch, sw, SWITCH_SETS[sw], None if ballast else L.NO_HEAVY)
+    g.set_triples(sh.s, sh.p, sh.o, sh.num_terms)
+    for strategy, clean in ALL_MODES:
+        what = (sh.name, sw, "s", strategy, clean)
+        g.run(sh.min_support, "s", clean, strategy)
+        t = g.test_paths()
+        print("paths", json.dumps({"cell": what, "n_dedup_members": int(t["n_dedup_members"]), "light_stage": bool(t["light_stage"]),
+                                   "n_light_items": int(t["n_light_items"]), "n_packed_octets": int(t["n_packed_octets"])}))
+        assert_shape_rows(g, sh, strategy, clean, "s", what)
+        assert compact_matches(g, sh.num_terms), what
+        check_shared_paths(t, sh, name, sw, strategy, what)
+
+
+def test_shared_objects_spo(monkeypatch):
+    """small300 with shared objects under projection spo."""
+    sh = L.shape("small300", shared_objects=True)
+    g = context(monkeypatch, "defaults", {}, L.NO_HEAVY)
+    g.set_triples(sh.s, sh.p, sh.o, sh.num_terms)
+    for strategy, clean in MODES:
+        what = (sh.name, "spo", strategy, clean)
+        g.run(sh.min_support, "spo", clean, strategy)
+        t = g.test_paths()
+        assert_shape_rows(g, sh, strategy, clean, "spo", what)
+        assert compact_matches(g, sh.num_terms), what
+        assert t["n_light_items"] > 0, what
+
+
+def test_shared_objects_association_rules(monkeypatch):
+    """small300 with shared objects and association rules on: o=O_k <=> p=P_k are rules (the oracle of
+    tests/test_gpu_ars.py, projection spo)."""
+    from tests.parity import ars_expected
+    from tests.test_gpu_ars import gpu_run
+    sh = L.shape("small300", shared_objects=True)
+    g = context(monkeypatch, "defaults", {}, L.NO_HEAVY)
+    arr = np.stack([sh.s, sh.p, sh.o], axis=1)
+    for strategy, clean in ((1, True), (0, False)):
+        rules, cinds = ars_expected(sh, strategy, clean)
+        got, got_rules = gpu_run(g, arr, sh.num_terms, sh.min_support, strategy, clean)
+        assert len(rules) > 0 and sorted(map(tuple, got_rules.tolist())) == rules, (strategy, clean)
+        assert got == cinds, (strategy, clean)
+
+
+def test_shard_report_needs_a_sharded_run():
+    """rdf_test_shard_report (the report tests/test_gpu_sharded_shapes.py reads) is a state error without a completed
+    sharded run; a one-GPU run does not count."""
+    sh = L.shape("pack32")
+    with _lib.Context(0) as g:
+        with pytest.raises(_lib.RdfError):
+            g.test_shard_report()
+        g.set_triples(sh.s, sh.p, sh.o, sh.num_terms)
+        g.run(sh.min_support, "s", True, 1)
+        with pytest.raises(_lib.RdfError):
+            g.test_shard_report()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the branches inside k_light (the instrumented variant)
 
 STATS_LIB = os.path.join(ROOT, "rdfind_amd", "librdfind_hip_stats.so")
