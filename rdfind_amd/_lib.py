@@ -129,7 +129,8 @@ class PathReport(ctypes.Structure):
                 ("light_side", ctypes.c_uint32), ("light_two_pass", ctypes.c_uint32), ("sig_on", ctypes.c_uint32),
                 ("piv2_on", ctypes.c_uint32), ("k3_hist", ctypes.c_uint32),
                 ("hclassed", ctypes.c_uint32), ("n_class_chunks", ctypes.c_uint64), ("n_emit_tiles", ctypes.c_uint64),
-                ("max_class_list", ctypes.c_uint64), ("n_multi_seg_lists", ctypes.c_uint64)]
+                ("max_class_list", ctypes.c_uint64), ("n_multi_seg_lists", ctypes.c_uint64),
+                ("k3_key_items", ctypes.c_uint64), ("k3_suppressed", ctypes.c_uint64)]
 
 
 class FcReport(ctypes.Structure):
@@ -930,7 +931,9 @@ class Context:
         flags light_ordered, light_side, light_two_pass, sig_on, piv2_on, k3_hist (K3 handed the record sort its first
         digit histogram).  Of the mask classes, as the run left them on the device: hclassed (binary heavy-only
         dependents read the class lists), n_class_chunks (k_class_eval work items), n_emit_tiles (k_class_emit tiles),
-        max_class_list (refs of the longest L'(m)) and n_multi_seg_lists (lists longer than one emission segment)."""
+        max_class_list (refs of the longest L'(m)) and n_multi_seg_lists (lists longer than one emission segment).  Of K3's
+        key items (RDFIND_EMIT_KEYS): k3_key_items (frequent binary keys the last build emitted from) and k3_suppressed
+        (records its triples left to them)."""
         r = PathReport()
         self._check(self._test_fn("rdf_test_paths")(self.ptr, ctypes.byref(r)), "rdf_test_paths")
         d = _struct_dict(r)

@@ -465,16 +465,33 @@ __device__ inline void bin_lookup3(const u64* __restrict__ lkeys, const u32* __r
 // rep (optional): bit k set for the records that repeat across triples of one subject or one (predicate, object) pair
 // (p[s], s[p], o[p], p[o]: the same predicate twice for a subject, the same typed object for many subjects); the others
 // (o[s], s[o] and the binary captures) practically never repeat within an emission iteration
+// supp (the emission has key items, item_records): a frequent binary key determines two unary records, which its key
+// item writes once (key_records), so a triple whose lookup hits the key does not write them: key (s, p) p[s] and s[p],
+// key (s, o) o[s] and s[o], key (p, o) o[p] and p[o].  A key's lookup then serves three records (its binary capture
+// and the two determined ones), so it is made whenever any join value is taken, and a partial selection loads all
+// three ranks.  logical (optional): the records the triple has before this rule (the run's n_records).
+// jv (optional): the join values of the three record groups (object, predicate, subject).
 template <bool LAZY>
 __device__ inline u32 triple_records(u64 i, const u32* __restrict__ s, const u32* __restrict__ p, const u32* __restrict__ o,
                                      u32 V, u32 twoU, const u32* __restrict__ frank, const u64* __restrict__ lkeys,
                                      const u32* __restrict__ lvals, u64 lmask, int proj, int joinbits, JoinSel js,
-                                     u64 (&rec)[9], u32* rep = nullptr, u32* grp = nullptr) {
+                                     bool supp, u64 (&rec)[9], u32* rep = nullptr, u32* grp = nullptr,
+                                     u32* logical = nullptr, u32* jv = nullptr) {
     u32 c = 0, rp_mask = 0;
     const u32 ts = s[i], tp = p[i], to = o[i];
+    if (jv) {
+        jv[0] = to;
+        jv[1] = tp;
+        jv[2] = ts;
+    }
     const bool jo = (proj & 4) && js.take(to), jp = (proj & 2) && js.take(tp), js_ = (proj & 1) && js.take(ts);
+    const bool any = jo || jp || js_;
     u32 rs, rp, ro;  // global condition ranks (or NONE)
-    if (LAZY) {
+    if (LAZY && supp) {
+        rs = any ? frank[ts] : NONE32;
+        rp = any ? frank[(u64)V + tp] : NONE32;
+        ro = any ? frank[2ull * V + to] : NONE32;
+    } else if (LAZY) {
         rs = jo || jp ? frank[ts] : NONE32;
         rp = jo || js_ ? frank[(u64)V + tp] : NONE32;
         ro = jp || js_ ? frank[2ull * V + to] : NONE32;
@@ -486,7 +503,7 @@ __device__ inline u32 triple_records(u64 i, const u32* __restrict__ s, const u32
     const bool fs = rs != NONE32, fp = rp != NONE32, fo = ro != NONE32;
     // the binary captures o[s,p], p[s,o], s[p,o]: their lookups in flight together (bin_lookup3)
     const u64 bkey[3] = {bin_key(2, ts, tp), bin_key(1, ts, to), bin_key(0, tp, to)};
-    const bool bneed[3] = {jo && fs && fp, jp && fs && fo, js_ && fp && fo};
+    const bool bneed[3] = {(supp ? any : jo) && fs && fp, (supp ? any : jp) && fs && fo, (supp ? any : js_) && fp && fo};
     u32 bval[3];
 #ifndef RDF_K3_LOOKUP3  // 1: bin_lookup3 (measured slower: c4 at 0.4 emit 54.1 -> 57.8 ms, c3 8.44 -> 8.88; its registers
 #define RDF_K3_LOOKUP3 0   // cost the write pass an occupancy step; profiles/r05_k3_lookup3_ab.log)
@@ -497,25 +514,95 @@ __device__ inline u32 triple_records(u64 i, const u32* __restrict__ s, const u32
 #pragma unroll
         for (int t = 0; t < 3; ++t) bval[t] = bneed[t] ? bin_lookup(lkeys, lvals, lmask, bkey[t]) : NONE32;
     }
+    // supp: the keys whose items write this triple's determined records
+    const bool ksp = supp && bval[0] != NONE32, kso = supp && bval[1] != NONE32, kpo = supp && bval[2] != NONE32;
+    u32 cut = 0;  // records the key items write in this triple's place
     if (jo) {  // project objects: o[s] (t4), o[p] (t5), o[s,p]
-        if (fs) rec[c++] = ((2ull * rs + 1) << joinbits) | to;
-        if (fp) { rp_mask |= 1u << c; rec[c++] = ((2ull * rp + 1) << joinbits) | to; }
+        if (fs) {
+            if (kso) ++cut;
+            else rec[c++] = ((2ull * rs + 1) << joinbits) | to;
+        }
+        if (fp) {
+            if (kpo) ++cut;
+            else { rp_mask |= 1u << c; rec[c++] = ((2ull * rp + 1) << joinbits) | to; }
+        }
         if (bval[0] != NONE32) rec[c++] = (((u64)twoU + bval[0]) << joinbits) | to;
     }
     const u32 co = c;
     if (jp) {  // project predicates: p[s] (t2), p[o] (t3), p[s,o]
-        if (fs) { rp_mask |= 1u << c; rec[c++] = ((2ull * rs) << joinbits) | tp; }
-        if (fo) { rp_mask |= 1u << c; rec[c++] = ((2ull * ro + 1) << joinbits) | tp; }
+        if (fs) {
+            if (ksp) ++cut;
+            else { rp_mask |= 1u << c; rec[c++] = ((2ull * rs) << joinbits) | tp; }
+        }
+        if (fo) {
+            if (kpo) ++cut;
+            else { rp_mask |= 1u << c; rec[c++] = ((2ull * ro + 1) << joinbits) | tp; }
+        }
         if (bval[1] != NONE32) rec[c++] = (((u64)twoU + bval[1]) << joinbits) | tp;
     }
     if (grp) *grp = co | ((c - co) << 2);  // records joined on the object, on the predicate (the rest: the subject)
     if (js_) {  // project subjects: s[p] (t0), s[o] (t1), s[p,o]
-        if (fp) { rp_mask |= 1u << c; rec[c++] = ((2ull * rp) << joinbits) | ts; }
-        if (fo) rec[c++] = ((2ull * ro) << joinbits) | ts;
+        if (fp) {
+            if (ksp) ++cut;
+            else { rp_mask |= 1u << c; rec[c++] = ((2ull * rp) << joinbits) | ts; }
+        }
+        if (fo) {
+            if (kso) ++cut;
+            else rec[c++] = ((2ull * ro) << joinbits) | ts;
+        }
         if (bval[2] != NONE32) rec[c++] = (((u64)twoU + bval[2]) << joinbits) | ts;
     }
     if (rep) *rep = rp_mask;
+    if (logical) *logical = c + cut;
     return c;
+}
+
+// records of key item b (at most 2): the two unary records frequent binary key b determines, each under the same
+// projection and take() tests as a triple's.  Key (a = v1, b = v2), a before b among s, p, o: the capture of a = v1 on
+// attribute b joined on v2, then the capture of b = v2 on attribute a joined on v1 (the order of a triple's groups:
+// object, predicate, subject).  A unary capture id is 2 rank + 1 when it projects the later of the two attributes the
+// condition leaves (triple_records).  They are unique by construction: no repeat flags
+__device__ inline u32 key_records(u64 b, const u64* __restrict__ bkeys, u32 V, const u32* __restrict__ frank, int proj,
+                                  int joinbits, JoinSel js, u64 (&rec)[9], u32* grp, u32* jv) {
+    const u64 k = bkeys[b];
+    int pa, pb;
+    bin_key_positions(bin_key_type(k), pa, pb);
+    const u32 v1 = bin_key_v1(k), v2 = bin_key_v2(k);
+    const u32 r1 = frank[(u64)pa * V + v1], r2 = frank[(u64)pb * V + v2];
+    u32 c = 0, co = 0, cp = 0;
+    if (jv) {
+        jv[0] = pb == 2 ? v2 : 0u;
+        jv[1] = pb == 1 ? v2 : pa == 1 ? v1 : 0u;
+        jv[2] = pa == 0 ? v1 : 0u;
+    }
+    if (r1 != NONE32 && ((proj >> pb) & 1) && js.take(v2)) {
+        rec[c++] = ((2ull * r1 + (pb == 2 ? 1u : 0u)) << joinbits) | v2;
+        if (pb == 2) ++co;
+        else ++cp;
+    }
+    if (r2 != NONE32 && ((proj >> pa) & 1) && js.take(v1)) {
+        rec[c++] = ((2ull * r2 + (pa == 1 ? 1u : 0u)) << joinbits) | v1;
+        if (pa == 1) ++cp;
+    }
+    if (grp) *grp = co | (cp << 2);
+    return c;
+}
+
+// The emission kernels work over items: item i < n is triple i, item n + b is key b of the binary lookup table's key
+// list (nk keys; 0: no key items, and the triples write every record themselves).  rep, grp as triple_records;
+// logical: the item's share of n_records (what the triples emit before the rule: a key item's records count nothing)
+template <bool LAZY>
+__device__ inline u32 item_records(u64 i, u64 n, u64 nk, const u64* __restrict__ bkeys, const u32* __restrict__ s,
+                                   const u32* __restrict__ p, const u32* __restrict__ o, u32 V, u32 twoU,
+                                   const u32* __restrict__ frank, const u64* __restrict__ lkeys,
+                                   const u32* __restrict__ lvals, u64 lmask, int proj, int joinbits, JoinSel js,
+                                   u64 (&rec)[9], u32* rep, u32* grp, u32* logical, u32* jv = nullptr) {
+    if (i < n)
+        return triple_records<LAZY>(i, s, p, o, V, twoU, frank, lkeys, lvals, lmask, proj, joinbits, js, nk != 0, rec, rep, grp,
+                                    logical, jv);
+    if (rep) *rep = 0;
+    *logical = 0;
+    return key_records(i - n, bkeys, V, frank, proj, joinbits, js, rec, grp, jv);
 }
 
 // two passes over contiguous per-block chunks of triples: COUNT writes each block's record count, the
@@ -543,6 +630,7 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_emit_records(const u32* __restric
                                                             const u32* __restrict__ lvals, u64 lmask, int proj,
                                                             int joinbits, JoinSel js, u64* block_counts,
                                                             const u64* __restrict__ block_offsets, u64* out, int recbits,
+                                                            u64 nk, const u64* __restrict__ bkeys, u64* kcnt,
                                                             u32* __restrict__ hist = nullptr, u32 hstride = 0, int w0 = 0) {
     static_assert(!HIST || WRITE, "the histogram belongs to the write pass");
     constexpr u32 HBIN = 1u << RS_MAX_BITS;
@@ -553,17 +641,27 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_emit_records(const u32* __restric
         for (u32 k = threadIdx.x; k < RDF_WAVES_PER_BLOCK * HBIN; k += RDF_BLOCK) whist[k] = 0;
         __syncthreads();
     }
+    // items [b, e) of the n triples and the nk key items behind them (item_records); kcnt (with key items): [0] the
+    // count pass's logical records (n_records: the slots no longer say it), [1] the records the triples left to the keys;
+    // nullptr: nobody reads them (an emission of a range build)
     const u64 b = (u64)blockIdx.x * per;
-    const u64 e = b + per < n ? b + per : n;
+    const u64 e = b + per < n + nk ? b + per : n + nk;
     if (!WRITE) {  // the block's record count: per-thread sums, one block reduction at the end
-        u32 mine = 0;
+        u32 mine = 0, lsum = 0;
         for (u64 i = b + threadIdx.x; i < e; i += RDF_BLOCK) {
             u64 rec[9];
-            mine += triple_records<LAZY>(i, s, p, o, V, twoU, frank, lkeys, lvals, lmask, proj, joinbits, js, rec);
+            u32 lg;
+            mine += item_records<LAZY>(i, n, nk, bkeys, s, p, o, V, twoU, frank, lkeys, lvals, lmask, proj, joinbits, js, rec,
+                                       nullptr, nullptr, &lg);
+            lsum += lg;
         }
         u32 total;
         block_exclusive_scan_u32(mine, lds_wave, &total);
         if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
+        if (nk && kcnt) {
+            block_exclusive_scan_u32(lsum, lds_wave, &total);
+            if (threadIdx.x == 0 && total) atomicAdd(&kcnt[0], (u64)total);
+        }
         return;
     }
     // region mode (block_offsets == nullptr, k_emit_compact after it): no count pass; the block writes its kept records
@@ -573,7 +671,8 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_emit_records(const u32* __restric
     u64 run = region ? rbase : block_offsets[blockIdx.x];
     const u64 lim = region ? rbase + 9ull * per : block_offsets[blockIdx.x + 1];
     bool over = false;
-    u64 emitted = 0;  // region mode: records emitted, repeats included (the run's n_records)
+    u64 emitted = 0;  // region mode: logical records (repeats and those left to the key items included: the run's n_records)
+    u32 cut = 0;      // the records this thread left to the key items (one block sum at the end)
 #ifndef RDF_EMIT_DEDUP
 #define RDF_EMIT_DEDUP 1
 #endif
@@ -586,10 +685,15 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_emit_records(const u32* __restric
     for (u64 i0 = b; i0 < e; i0 += RDF_BLOCK) {
         const u64 i = i0 + threadIdx.x;
         u64 rec[9];
-        u32 c = 0, rep = 0, grp = 0;
+        // rep, one register across the table lookups, carries three fields: bits 0..8 the repeat flags of the records,
+        // bits 16..19 (HIST) the group counts (two bits each: joined on the object, on the predicate), bits 20..23 the
+        // item's logical record count (<= 9).  Every use masks its field: the flags by (1 << c) - 1, the counts by & 3
+        u32 c = 0, rep = 0, grp = 0, lg = 0;
         if (i < e)
-            c = triple_records<LAZY>(i, s, p, o, V, twoU, frank, lkeys, lvals, lmask, proj, joinbits, js, rec, &rep,
-                                     HIST ? &grp : nullptr);
+            c = item_records<LAZY>(i, n, nk, bkeys, s, p, o, V, twoU, frank, lkeys, lvals, lmask, proj, joinbits, js, rec, &rep,
+                                   HIST ? &grp : nullptr, &lg);
+        cut += lg > c ? lg - c : 0u;  // (a key item has records and no logical ones)
+        rep |= lg << 20;              // (<= 9; with HIST's groups in one register across the table lookups)
         if (HIST) rep |= grp << 16;  // (one register across the table lookups: the write pass's occupancy step)
         // Records repeated within the iteration's 256 triples (the same subject's predicate, the same (predicate,
         // object) pair: ~23 % of c2's records; only the kinds flagged by triple_records are looked up) are written
@@ -651,10 +755,12 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_emit_records(const u32* __restric
             }
         }
         // one scan of (kept, emitted) packed in 16-bit halves (each <= 9 x 256): this thread's kept records go to the
-        // front of the iteration's region, its dropped ones become padding behind all kept records
-        const u32 nk = (u32)__popc(keep);
+        // front of the iteration's region, its dropped ones become padding behind all kept records.  Region mode has
+        // no padding: its upper half sums the logical records
+        const u32 nkept = (u32)__popc(keep);
         u32 tot;
-        const u32 off = block_exclusive_scan_u32(nk | (c << 16), lds_wave, &tot);
+        const u32 off = block_exclusive_scan_u32(nkept | ((region ? rep >> 20 : c) << 16), lds_wave, &tot);
+        tot = (u32)__builtin_amdgcn_readfirstlane((int)tot);  // (the block's sums: the region cursor stays in scalars)
         const u32 kept = tot & 0xffffu, total = tot >> 16;
         u64 q = run + (off & 0xffffu);
 #pragma unroll
@@ -670,7 +776,7 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_emit_records(const u32* __restric
             continue;
         }
         u64 pq = run + kept + ((off >> 16) - (off & 0xffffu));
-        for (u32 k = nk; k < c; ++k, ++pq) {
+        for (u32 k = nkept; k < c; ++k, ++pq) {
             if (pq < lim) out[pq] = EMIT_PAD;
             else over = true;
         }
@@ -691,6 +797,11 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_emit_records(const u32* __restric
         }
     }
     if (!region && over) atomicOr((unsigned long long*)block_counts, 1ull);
+    if (nk && kcnt) {
+        u32 bsum;
+        block_exclusive_scan_u32(cut, lds_wave, &bsum);
+        if (threadIdx.x == 0 && bsum) atomicAdd(&kcnt[1], (u64)bsum);
+    }
 }
 
 // region mode's compaction: block b's kept records [9 x per x b, + cnt[b]) -> dst[off[b], + cnt[b]) (coalesced, 4 loads
@@ -735,7 +846,8 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_emit_ranges(const u32* __restrict
                                                            const u32* __restrict__ lvals, u64 lmask, int proj,
                                                            int joinbits, JoinSel js, const u32* __restrict__ rlo_g, u32 nr,
                                                            u64* overflow, const u64* __restrict__ block_offsets,
-                                                           u64* out, int recbits) {
+                                                           u64* out, int recbits, u64 nk,
+                                                           const u64* __restrict__ bkeys) {
     __shared__ u32 rlo[EMIT_MAX_RANGES];
     __shared__ u32 cur[EMIT_MAX_RANGES];
     __shared__ u64 base[EMIT_MAX_RANGES];
@@ -752,14 +864,16 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_emit_ranges(const u32* __restrict
         for (u32 k = threadIdx.x; k < (u32)EMIT_DEDUP_SLOTS; k += RDF_BLOCK) htab[k] = 0;  // tag 0: empty
     __syncthreads();
     const u64 b = (u64)blockIdx.x * per;
-    const u64 e = b + per < n ? b + per : n;
+    const u64 e = b + per < n + nk ? b + per : n + nk;  // items: the triples, then the key items (item_records)
     u32 tag = 0;
     bool over = false;
     for (u64 i0 = b; i0 < e; i0 += RDF_BLOCK) {
         const u64 i = i0 + threadIdx.x;
         u64 rec[9];
-        u32 c = 0, rep = 0, grp = 0;
-        if (i < e) c = triple_records<LAZY>(i, s, p, o, V, twoU, frank, lkeys, lvals, lmask, proj, joinbits, js, rec, &rep, &grp);
+        u32 c = 0, rep = 0, grp = 0, lg = 0, jv[3] = {0u, 0u, 0u};
+        if (i < e)
+            c = item_records<LAZY>(i, n, nk, bkeys, s, p, o, V, twoU, frank, lkeys, lvals, lmask, proj, joinbits, js, rec, &rep,
+                                   &grp, &lg, jv);
         const u32 co = grp & 3u, cp = (grp >> 2) & 3u, cs = c - co - cp;
         u32 keep = (1u << c) - 1u;
         if (dedup) {  // as k_emit_records: the repeating kinds through the iteration's LDS table, the others kept
@@ -796,9 +910,9 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_emit_ranges(const u32* __restrict
         // one LDS cursor claim per attribute group (its join value: o, p or s of the triple)
         u32 ro = 0, rp = 0, rs = 0;
         u64 qo = 0, qp = 0, qs = 0;
-        if (co) ro = range_of(rlo, nr, o[i]);
-        if (cp) rp = range_of(rlo, nr, p[i]);
-        if (cs) rs = range_of(rlo, nr, s[i]);
+        if (co) ro = range_of(rlo, nr, jv[0]);
+        if (cp) rp = range_of(rlo, nr, jv[1]);
+        if (cs) rs = range_of(rlo, nr, jv[2]);
         if (co) qo = base[ro] + atomicAdd(&cur[ro], co);
         if (cp) qp = base[rp] + atomicAdd(&cur[rp], cp) - co;
         if (cs) qs = base[rs] + atomicAdd(&cur[rs], cs) - co - cp;
@@ -1132,7 +1246,8 @@ __global__ __launch_bounds__(JH_BLOCK) void k_emit_join_bhist(const u32* __restr
                                                                const u32* __restrict__ o, u64 n, u64 per, u32 V, u32 twoU,
                                                                const u32* __restrict__ frank, const u64* __restrict__ lkeys,
                                                                const u32* __restrict__ lvals, u64 lmask, int proj,
-                                                               int joinbits, JoinSel own, int jshift, u32* bh, u64* hist) {
+                                                               int joinbits, JoinSel own, int jshift, u32* bh, u64* hist,
+                                                               u64 nk, const u64* __restrict__ bkeys, u64* kcnt) {
     __shared__ u32 lh[JH_BUCKETS];
     for (u32 k = threadIdx.x; k < JH_BUCKETS; k += JH_BLOCK) lh[k] = 0;
     __syncthreads();
@@ -1140,16 +1255,25 @@ __global__ __launch_bounds__(JH_BLOCK) void k_emit_join_bhist(const u32* __restr
     all.lo = 0u;
     all.hi = JOIN_ALL_HI;
     const u64 b = (u64)blockIdx.x * per;
-    const u64 e = b + per < n ? b + per : n;
+    const u64 e = b + per < n + nk ? b + per : n + nk;  // items: the triples, then the key items (item_records)
+    u32 lsum = 0, cut = 0;  // with key items: the logical records (n_records) and those the triples left to the keys
     for (u64 i = b + threadIdx.x; i < e; i += JH_BLOCK) {
         u64 rec[9];
-        u32 grp = 0;
-        const u32 c = triple_records<LAZY>(i, s, p, o, V, twoU, frank, lkeys, lvals, lmask, proj, joinbits, all, rec,
-                                           nullptr, &grp);
+        u32 grp = 0, lg = 0, jv[3];
+        const u32 c = item_records<LAZY>(i, n, nk, bkeys, s, p, o, V, twoU, frank, lkeys, lvals, lmask, proj, joinbits, all,
+                                         rec, nullptr, &grp, &lg, jv);
         const u32 co = grp & 3u, cp = (grp >> 2) & 3u, cs = c - co - cp;
-        if (co) atomicAdd(&lh[o[i] >> jshift], co);
-        if (cp) atomicAdd(&lh[p[i] >> jshift], cp);
-        if (cs) atomicAdd(&lh[s[i] >> jshift], cs);
+        if (co) atomicAdd(&lh[jv[0] >> jshift], co);
+        if (cp) atomicAdd(&lh[jv[1] >> jshift], cp);
+        if (cs) atomicAdd(&lh[jv[2] >> jshift], cs);
+        lsum += lg;
+        if (i < n) cut += lg - c;
+    }
+    if (nk) {
+        lsum = wave_sum(lsum);
+        cut = wave_sum(cut);
+        if (lane_id() == 0 && lsum) atomicAdd(&kcnt[0], (u64)lsum);
+        if (lane_id() == 0 && cut) atomicAdd(&kcnt[1], (u64)cut);
     }
     __syncthreads();
     u32* row = bh + (u64)blockIdx.x * JH_BUCKETS;

@@ -314,6 +314,8 @@ struct rdf_ctx : CtxBuffers {
     u64 shrep_vC = ~0ull;
     // the last group build's K3 handed the record sort its first digit histogram (RDFIND_EMIT_HIST)
     bool k3_hist = false;
+    // ... and its emission's key items (RDFIND_EMIT_KEYS) and the records its triples left to them (rdf_test_paths)
+    u64 k3_key_items = 0, k3_suppressed = 0;
     // what the light launches of the last discovery were given (d_light_kernels; sums over its pages, ranges and
     // passes), for rdf_test_paths
     struct LightPaths {
@@ -2122,6 +2124,7 @@ static rdf_status g_record_bits(rdf_ctx* c) {
     c->n_dense = c->n_dense_eligible = c->n_dedup_members = 0;
     c->path_k3 = 0;
     c->k3_hist = false;
+    c->k3_key_items = c->k3_suppressed = 0;
     const u32 V = c->V ? c->V : 1;
     const u64 ncap = 2ull * c->U + c->B;  // compact candidate captures (k_frank_final)
     const int capbits = bits_for(ncap ? ncap - 1 : 0);
@@ -2143,6 +2146,9 @@ static JoinSel shard_sel(const rdf_ctx* c) {
     }
     return js;
 }
+
+// key items of the K3 emission (kernels.inl item_records): the keys of the binary lookup table, behind the n triples
+static u64 emit_key_items(const rdf_ctx* c) { return c->sw.emit_keys && c->n ? c->B : 0; }
 
 // K3 emission of the selected join values (record buffers of cap_rec slots), K4 sort by (capture, join), K5 fresh
 // records per record tile (tile_fresh, tile_base) and the records' supports -> sup[ncap].  The sorted records are left in
@@ -2180,9 +2186,16 @@ static rdf_status g_emit_range(rdf_ctx* c, int proj, JoinSel js, u64 cap_rec, u3
     const int slot = cache > 0 ? cache - 1 : cache < 0 ? -cache - 1 : -1;
     // the selection takes a part of the join values (a join range, or a rank's shard): lazy condition-rank loads
     const bool lazy = js.nranks > 1 || js.lo != 0u || js.hi != JOIN_ALL_HI;
+    // the emission's items: the n triples, then the nk key items (whatever sizes by the emission sizes by ni)
+    const u64 nk = emit_key_items(c), ni = n + nk;
+    const u64* bk = c->bkeys.as<u64>();
+    // (zeroed above) with key items: the count pass's logical records, the records left to the keys.  A range build
+    // (cache != 0) takes both from its histogram pass: its emissions count neither
+    u64* kcnt = cache == 0 ? dscal(c, 10) : nullptr;
+    c->k3_key_items = nk;
     const unsigned eg =
-        grid_for(n, RDF_BLOCK, c->sw.emit_grid ? (unsigned)std::min<u64>(c->sw.emit_grid, kEmitGrid) : kEmitGrid);
-    const u64 per = n ? (n + eg - 1) / eg : 0;
+        grid_for(ni, RDF_BLOCK, c->sw.emit_grid ? (unsigned)std::min<u64>(c->sw.emit_grid, kEmitGrid) : kEmitGrid);
+    const u64 per = n ? (ni + eg - 1) / eg : 0;
     ENSURE(c, eblk, 2 * (eg + 2ull) * 8);
     const bool reuse = cache < 0 && slot < (int)c->ecache_je.size();
     u64* overflow = (u64*)dscal(c, 8);  // the write pass's overflow word (zeroed above)
@@ -2190,7 +2203,7 @@ static rdf_status g_emit_range(rdf_ctx* c, int proj, JoinSel js, u64 cap_rec, u3
     // into its own region of rec_tmp (9 x per slots), then k_emit_compact packs the regions into rec by the scanned
     // block counts; no padding reaches the sort.  c2 emit 0.86 -> 0.73 ms, sort 1.79 -> 1.71, c3 step 72.4 -> 69.9 ms
     // (profiles/r05_emit_onepass_ab.log).  RDFIND_EMIT_ONEPASS=0: the count pass + write pass with padding
-    const bool onepass = c->sw.emit_onepass && cache == 0 && slot_cap >= 9 * n;
+    const bool onepass = c->sw.emit_onepass && cache == 0 && slot_cap >= 9 * ni;
     if (n) c->path_k3 = std::max<u32>(c->path_k3, onepass ? RDF_TEST_K3_ONEPASS : RDF_TEST_K3_TWOPASS);
     // ... and the emission blocks count the record sort's first digit themselves (k_emit_records<.., HIST>): the sort's
     // first pass scatters the regions straight into rec (radix_seg_first_pass), so the regions are not compacted, the
@@ -2210,24 +2223,26 @@ static rdf_status g_emit_range(rdf_ctx* c, int proj, JoinSel js, u64 cap_rec, u3
         if (lazy)
             hipLaunchKernelGGL((k_emit_records<true, true, true>), dim3(eg), dim3(RDF_BLOCK), 0, st, c->s, c->p, c->o, n, per, V,
                                2u * c->U, c->frank.as<u32>(), c->lkeys.as<u64>(), c->lvals.as<u32>(), c->lcap - 1, proj,
-                               joinbits, js, eb, (const u64*)nullptr, c->rec_tmp.as<u64>(), bits, hist, hs, w0);
+                               joinbits, js, eb, (const u64*)nullptr, c->rec_tmp.as<u64>(), bits, nk, bk, kcnt, hist, hs, w0);
         else
             hipLaunchKernelGGL((k_emit_records<true, false, true>), dim3(eg), dim3(RDF_BLOCK), 0, st, c->s, c->p, c->o, n, per, V,
                                2u * c->U, c->frank.as<u32>(), c->lkeys.as<u64>(), c->lvals.as<u32>(), c->lcap - 1, proj,
-                               joinbits, js, eb, (const u64*)nullptr, c->rec_tmp.as<u64>(), bits, hist, hs, w0);
+                               joinbits, js, eb, (const u64*)nullptr, c->rec_tmp.as<u64>(), bits, nk, bk, kcnt, hist, hs, w0);
         HIP_TRY(c, hipGetLastError());
         tend(c, RDF_T_EMIT);
         tbegin(c, RDF_T_SORT);
         HIP_TRY(c, radix_seg_first_pass(c->ws, c->rec_tmp.as<u64>(), slot_cap, ebuf, slot_cap, nullptr, 9 * per, eb, eg, w0, hist,
                                         over32, st));
-        u64 v[3];
-        TRY(read_multi(c, {{eb + eg + 1, 8}, {eb + eg, 8}, {over32, 4}}, v));
+        u64 v[4];
+        TRY(read_multi(c, {{eb + eg + 1, 8}, {eb + eg, 8}, {over32, 4}, {kcnt + 1, 8}}, v));
         if (v[2])
             return fail(c, RDF_ERR_LIMIT, "K3: the emission's digit histogram and its records disagree (the sort's first "
                                           "pass wrote nothing past its buffer)");
         const u64 Je = v[0];  // the kept records, all of them sorted; the emitted ones count as n_records
         if (Je > slot_cap) return fail(c, RDF_ERR_LIMIT, "K3 emitted more records than the join range was sized for");
-        c->J_emit += std::max(v[1], Je);
+        // (with key items the kept records may outnumber the triples' logical ones: the keys' records count nothing)
+        c->J_emit += nk ? v[1] : std::max(v[1], Je);
+        c->k3_suppressed += v[3];
         c->k3_hist = true;
         u64 *keys = ebuf, *tmp = c->rec_tmp.as<u64>();
         HIP_TRY(c, radix_sort_u64_rest(c->ws, keys, tmp, Je, w0, bits, st));
@@ -2241,11 +2256,11 @@ static rdf_status g_emit_range(rdf_ctx* c, int proj, JoinSel js, u64 cap_rec, u3
         if (lazy)
             hipLaunchKernelGGL((k_emit_records<true, true>), dim3(eg), dim3(RDF_BLOCK), 0, st, c->s, c->p, c->o, n, per, V,
                                2u * c->U, c->frank.as<u32>(), c->lkeys.as<u64>(), c->lvals.as<u32>(), c->lcap - 1, proj,
-                               joinbits, js, c->eblk.as<u64>(), (const u64*)nullptr, c->rec_tmp.as<u64>(), capbits + joinbits);
+                               joinbits, js, c->eblk.as<u64>(), (const u64*)nullptr, c->rec_tmp.as<u64>(), capbits + joinbits, nk, bk, kcnt);
         else
             hipLaunchKernelGGL((k_emit_records<true, false>), dim3(eg), dim3(RDF_BLOCK), 0, st, c->s, c->p, c->o, n, per, V,
                                2u * c->U, c->frank.as<u32>(), c->lkeys.as<u64>(), c->lvals.as<u32>(), c->lcap - 1, proj,
-                               joinbits, js, c->eblk.as<u64>(), (const u64*)nullptr, c->rec_tmp.as<u64>(), capbits + joinbits);
+                               joinbits, js, c->eblk.as<u64>(), (const u64*)nullptr, c->rec_tmp.as<u64>(), capbits + joinbits, nk, bk, kcnt);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, exclusive_scan_u64(c->ws, c->eblk.as<u64>(), eoff, eg, dscal(c, 0), st));
         hipLaunchKernelGGL(k_emit_compact, dim3(eg), dim3(RDF_BLOCK), 0, st, c->rec_tmp.as<u64>(), 9 * per,
@@ -2254,6 +2269,7 @@ static rdf_status g_emit_range(rdf_ctx* c, int proj, JoinSel js, u64 cap_rec, u3
         HIP_TRY(c, hipMemcpyAsync(dscal(c, 3), c->eblk.as<u64>() + eg, 8, hipMemcpyDeviceToDevice, st));
     }
     u64 je_early = ~0ull;  // the slot count, when read before the write pass
+    u64 kc[2] = {0, 0};    // with key items: the logical records of a count pass, the records left to the keys
     if (cache > 0) {
         if ((int)c->ecache_je.size() <= slot) c->ecache_je.resize(slot + 1);
         HIP_TRY(c, c->ecache.grow_keep((size_t)(slot + 1) * ECACHE_STRIDE * 8, st));
@@ -2267,18 +2283,18 @@ static rdf_status g_emit_range(rdf_ctx* c, int proj, JoinSel js, u64 cap_rec, u3
             if (lazy)
                 hipLaunchKernelGGL((k_emit_records<false, true>), dim3(eg), dim3(RDF_BLOCK), 0, st, c->s, c->p, c->o, n, per, V,
                                    2u * c->U, c->frank.as<u32>(), c->lkeys.as<u64>(), c->lvals.as<u32>(), c->lcap - 1, proj,
-                                   joinbits, js, c->eblk.as<u64>(), (const u64*)nullptr, (u64*)nullptr, capbits + joinbits);
+                                   joinbits, js, c->eblk.as<u64>(), (const u64*)nullptr, (u64*)nullptr, capbits + joinbits, nk, bk, kcnt);
             else
                 hipLaunchKernelGGL((k_emit_records<false, false>), dim3(eg), dim3(RDF_BLOCK), 0, st, c->s, c->p, c->o, n, per, V,
                                    2u * c->U, c->frank.as<u32>(), c->lkeys.as<u64>(), c->lvals.as<u32>(), c->lcap - 1, proj,
-                                   joinbits, js, c->eblk.as<u64>(), (const u64*)nullptr, (u64*)nullptr, capbits + joinbits);
+                                   joinbits, js, c->eblk.as<u64>(), (const u64*)nullptr, (u64*)nullptr, capbits + joinbits, nk, bk, kcnt);
             HIP_TRY(c, hipGetLastError());
             HIP_TRY(c, exclusive_scan_u64(c->ws, c->eblk.as<u64>(), c->eblk.as<u64>(), eg, c->eblk.as<u64>() + eg, st));
             HIP_TRY(c, hipMemcpyAsync(dscal(c, 0), c->eblk.as<u64>() + eg, 8, hipMemcpyDeviceToDevice, st));
             if (cache > 0)
                 HIP_TRY(c, hipMemcpyAsync(c->ecache.as<u64>() + (u64)slot * ECACHE_STRIDE, c->eblk.p, (eg + 1ull) * 8ull,
                                           hipMemcpyDeviceToDevice, st));
-            if (slot_cap < 9 * n) {  // a join range's buffers: the slot count is checked before the write pass
+            if (slot_cap < 9 * ni) {  // a join range's buffers: the slot count is checked before the write pass
                 TRY(read_scalars(c, 1));
                 je_early = c->hscal[0];
                 if (je_early > slot_cap)
@@ -2288,11 +2304,11 @@ static rdf_status g_emit_range(rdf_ctx* c, int proj, JoinSel js, u64 cap_rec, u3
         if (lazy)
             hipLaunchKernelGGL((k_emit_records<true, true>), dim3(eg), dim3(RDF_BLOCK), 0, st, c->s, c->p, c->o, n, per, V,
                                2u * c->U, c->frank.as<u32>(), c->lkeys.as<u64>(), c->lvals.as<u32>(), c->lcap - 1, proj,
-                               joinbits, js, overflow, c->eblk.as<u64>(), ebuf, capbits + joinbits);
+                               joinbits, js, overflow, c->eblk.as<u64>(), ebuf, capbits + joinbits, nk, bk, kcnt);
         else
             hipLaunchKernelGGL((k_emit_records<true, false>), dim3(eg), dim3(RDF_BLOCK), 0, st, c->s, c->p, c->o, n, per, V,
                                2u * c->U, c->frank.as<u32>(), c->lkeys.as<u64>(), c->lvals.as<u32>(), c->lcap - 1, proj,
-                               joinbits, js, overflow, c->eblk.as<u64>(), ebuf, capbits + joinbits);
+                               joinbits, js, overflow, c->eblk.as<u64>(), ebuf, capbits + joinbits, nk, bk, kcnt);
         HIP_TRY(c, hipGetLastError());
     }
     tend(c, RDF_T_EMIT);
@@ -2310,15 +2326,29 @@ static rdf_status g_emit_range(rdf_ctx* c, int proj, JoinSel js, u64 cap_rec, u3
         Je = c->ecache_je[slot];
     } else {
         if (je_early == ~0ull) {
-            TRY(read_scalars(c, onepass ? 4 : 1));
+            if (nk && kcnt) {  // ... and the key items' two counters in the same read-back
+                u64 v[6];
+                TRY(read_multi(c, {{dscal(c, 0), 8}, {dscal(c, 1), 8}, {dscal(c, 2), 8}, {dscal(c, 3), 8}, {kcnt, 8}, {kcnt + 1, 8}}, v));
+                for (int k = 0; k < 4; ++k) c->hscal[k] = v[k];
+                kc[0] = v[4];
+                kc[1] = v[5];
+            } else {
+                TRY(read_scalars(c, onepass ? 4 : 1));
+            }
             je_early = c->hscal[0];
             // one pass: the kept records are sorted, the emitted ones (repeats included) count as n_records
-            if (onepass && n && c->hscal[3] >= je_early) c->J_emit += c->hscal[3] - je_early;
+            if (!nk && onepass && n && c->hscal[3] >= je_early) c->J_emit += c->hscal[3] - je_early;
         }
         Je = je_early;
         if (cache > 0) c->ecache_je[slot] = Je;
     }
     if (Je > slot_cap) return fail(c, RDF_ERR_LIMIT, "K3 emitted more records than the join range was sized for");
+    if (nk && kcnt) {
+        // n_records stays what the triples emit before the rule: not the slots (g_sort_support adds Je), which hold the
+        // key items' records and lack the ones left to them.  (A range build takes both numbers from its histogram pass)
+        c->J_emit += (onepass ? c->hscal[3] : kc[0]) - Je;  // (u64 arithmetic: the sum with Je is the logical count)
+        c->k3_suppressed += kc[1];
+    }
     return g_sort_support(c, ebuf, c->rec_tmp.as<u64>(), Je, sup, Jout, nullptr);
 }
 
@@ -2377,7 +2407,7 @@ static rdf_status g_emit_sort_support(rdf_ctx* c, int proj) {
     c->sort_passes_records = 0;
     ENSURE(c, support, std::max<u64>(c->ncap, 1) * 4);
     u64 J = 0;
-    TRY(g_emit_range(c, proj, shard_sel(c), 9 * c->n, c->support.as<u32>(), &J));
+    TRY(g_emit_range(c, proj, shard_sel(c), 9 * (c->n + emit_key_items(c)), c->support.as<u32>(), &J));
     c->J = J;
     return RDF_OK;
 }
@@ -2573,8 +2603,10 @@ static rdf_status g_emit_all_ranges(rdf_ctx* c, int proj, JoinSel own) {
     lo[2 * nr] = JH_BUCKETS;
     ENSURE(c, jrmap, (2 * nr + 1) * 4ull);
     HIP_TRY(c, ctx_copy(c, c->jrmap.p, lo.data(), (2 * nr + 1) * 4ull, hipMemcpyHostToDevice));
-    const unsigned eg = grid_for(n, RDF_BLOCK, kRangeEmitGrid);
-    const u64 per = n ? (n + eg - 1) / eg : 0;
+    const u64 nk = emit_key_items(c), ni = n + nk;  // the emission's items, as g_ranges_supports counted them
+    const u64* bk = c->bkeys.as<u64>();
+    const unsigned eg = grid_for(ni, RDF_BLOCK, kRangeEmitGrid);
+    const u64 per = n ? (ni + eg - 1) / eg : 0;
     const u64 nb = (u64)nr * eg;
     ENSURE(c, eblk, (nb + 1) * 8);
     HIP_TRY(c, hipMemsetAsync(c->scal.p, 0, 16 * sizeof(u64), st));
@@ -2599,11 +2631,11 @@ static rdf_status g_emit_all_ranges(rdf_ctx* c, int proj, JoinSel own) {
         if (lazy)
             hipLaunchKernelGGL((k_emit_ranges<true>), dim3(eg), dim3(RDF_BLOCK), 0, st, c->s, c->p, c->o, n, per, V, twoU,
                                c->frank.as<u32>(), c->lkeys.as<u64>(), c->lvals.as<u32>(), c->lcap - 1, proj, c->joinbits, own,
-                               c->jrmap.as<u32>(), nr, overflow, c->eblk.as<u64>(), c->rstore.as<u64>(), recbits);
+                               c->jrmap.as<u32>(), nr, overflow, c->eblk.as<u64>(), c->rstore.as<u64>(), recbits, nk, bk);
         else
             hipLaunchKernelGGL((k_emit_ranges<false>), dim3(eg), dim3(RDF_BLOCK), 0, st, c->s, c->p, c->o, n, per, V, twoU,
                                c->frank.as<u32>(), c->lkeys.as<u64>(), c->lvals.as<u32>(), c->lcap - 1, proj, c->joinbits, own,
-                               c->jrmap.as<u32>(), nr, overflow, c->eblk.as<u64>(), c->rstore.as<u64>(), recbits);
+                               c->jrmap.as<u32>(), nr, overflow, c->eblk.as<u64>(), c->rstore.as<u64>(), recbits, nk, bk);
         HIP_TRY(c, hipGetLastError());
         // every (range, block) region ends at the next offset; records past it were not written
         TRY(read_u64(c, overflow, &c->hscal[8]));
@@ -2631,24 +2663,30 @@ static rdf_status g_ranges_supports(rdf_ctx* c, int proj, u64 max_range, JoinSel
     ENSURE(c, jhist, JH_BUCKETS * 8);
     HIP_TRY(c, hipMemsetAsync(c->jhist.p, 0, JH_BUCKETS * 8, st));
     // the blocks of the emission (g_emit_all_ranges): their bucket histograms give its per-range block offsets
-    const unsigned eg = grid_for(n, RDF_BLOCK, kRangeEmitGrid);
-    const u64 per = n ? (n + eg - 1) / eg : 0;
+    const u64 nk = emit_key_items(c), ni = n + nk;  // the emission's items: the triples, then the key items
+    const u64* bk = c->bkeys.as<u64>();
+    u64* kcnt = dscal(c, 10);  // with key items: the logical records (n_records), the records left to the keys
+    HIP_TRY(c, hipMemsetAsync(kcnt, 0, 16, st));
+    const unsigned eg = grid_for(ni, RDF_BLOCK, kRangeEmitGrid);
+    const u64 per = n ? (ni + eg - 1) / eg : 0;
     ENSURE(c, jbh, (u64)eg * JH_BUCKETS * 4);
     tbegin(c, RDF_T_EMIT);
     if (n) {
         if (own.nranks > 1)
             hipLaunchKernelGGL(k_emit_join_bhist<true>, dim3(eg), dim3(JH_BLOCK), 0, st, c->s, c->p, c->o, n, per, V, 2u * c->U,
                                c->frank.as<u32>(), c->lkeys.as<u64>(), c->lvals.as<u32>(), c->lcap - 1, proj, joinbits, own,
-                               jshift, c->jbh.as<u32>(), c->jhist.as<u64>());
+                               jshift, c->jbh.as<u32>(), c->jhist.as<u64>(), nk, bk, kcnt);
         else
             hipLaunchKernelGGL(k_emit_join_bhist<false>, dim3(eg), dim3(JH_BLOCK), 0, st, c->s, c->p, c->o, n, per, V, 2u * c->U,
                                c->frank.as<u32>(), c->lkeys.as<u64>(), c->lvals.as<u32>(), c->lcap - 1, proj, joinbits, own,
-                               jshift, c->jbh.as<u32>(), c->jhist.as<u64>());
+                               jshift, c->jbh.as<u32>(), c->jhist.as<u64>(), nk, bk, kcnt);
         HIP_TRY(c, hipGetLastError());
     }
     tend(c, RDF_T_EMIT);
     std::vector<u64> h(JH_BUCKETS);
+    u64 kc[2] = {0, 0};
     HIP_TRY(c, hipMemcpyAsync(h.data(), c->jhist.p, JH_BUCKETS * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(kc, kcnt, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     std::vector<rdf_ctx::JoinRange>& ranges = c->jranges;
     ranges.clear();
@@ -2695,6 +2733,11 @@ static rdf_status g_ranges_supports(rdf_ctx* c, int proj, u64 max_range, JoinSel
                                c->rsup.as<u32>(), ncap);
     }
     c->J = Jtot;
+    if (nk) {  // n_records: what the triples emit before the rule (the ranges' slots hold the keys' records instead)
+        c->J_emit = kc[0];
+        c->k3_suppressed = kc[1];
+    }
+    c->k3_key_items = nk;
     return RDF_OK;
 }
 
@@ -2988,7 +3031,7 @@ rdf_status rdf_build_capture_groups(rdf_ctx* c, const char* projection, rdf_grou
     c->shrep_done = false;
     c->paged = c->cs_open = c->cs_top_valid = c->sel_valid = false;
     c->n_group_ranges = 1;
-    if (c->sw.group_range_records || 9 * c->n >= (1ull << 32)) {
+    if (c->sw.group_range_records || 9 * (c->n + emit_key_items(c)) >= (1ull << 32)) {
         TRY(g_build_ranges(c, proj, c->sw.group_range_records ? c->sw.group_range_records : auto_range_records(c)));
     } else {
         TRY(g_emit_sort_support(c, proj));
@@ -4692,10 +4735,10 @@ static rdf_status sh_phase14(rdf_ctx* c, rdf_exchange* req) {
     c->sh_m = m;
     // a join shard whose K3 records exceed one sort's u32 offsets (>= 2^32/9 received triples, e.g. c4 at 10^9 triples
     // over 2 or 4 ranks) builds its groups in join ranges, as one GPU does: pass 1 here, pass 2 after the all-reduce
-    c->sh_ranged = c->sw.group_range_records || 9 * m >= (1ull << 32);
     c->n_group_ranges = 1;
     {
         ReceivedTriples rt(c);  // K3 reads the received triples; the resident input stays this rank's slice
+        c->sh_ranged = c->sw.group_range_records || 9 * (c->n + emit_key_items(c)) >= (1ull << 32);  // (the emission's items)
         if (c->sh_ranged) {
             TRY(g_ranges_supports(c, c->sh_proj, c->sw.group_range_records ? c->sw.group_range_records : auto_range_records(c),
                                   shard_sel(c)));

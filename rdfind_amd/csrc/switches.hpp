@@ -67,6 +67,8 @@ static inline RankPhase rank_phase(const char* v) {  // "rank:phase"; anything e
        "0: K3 as count pass + write pass (as when the record buffers hold fewer than 9 records per triple)") \
     SW(emit_hist, bool, true, "RDFIND_EMIT_HIST", atoi(v) != 0, AB, \
        "0: the one-pass K3 compacts its regions and the record sort counts its first digit itself (no histogram from K3)") \
+    SW(emit_keys, bool, true, "RDFIND_EMIT_KEYS", atoi(v) != 0, AB, \
+       "0: K3 has no key items: every triple writes the two unary records its frequent binary keys determine") \
     SW(emit_grid, u64, 0, "RDFIND_EMIT_GRID", strtoull(v, nullptr, 10), TEST, \
        "=<blocks>: cap of K3's emission grid (small: a small input's blocks emit regions of several sort sub-tiles)") \
     /* cinds: the pivot pass and the light passes */ \

@@ -133,6 +133,9 @@ typedef struct rdf_test_path_report {
     uint64_t n_emit_tiles;         /* k_class_emit tiles of the class part (member tiles x list segments) */
     uint64_t max_class_list;       /* refs of the longest class list L'(m) */
     uint64_t n_multi_seg_lists;    /* class lists longer than one emission segment (CLS_LS refs) */
+    /* K3's key items (RDFIND_EMIT_KEYS) of the last group build; a rank of a sharded run reports its own */
+    uint64_t k3_key_items;         /* frequent binary keys the emission took as items behind the triples (0: switch off) */
+    uint64_t k3_suppressed;        /* records the triples left to those items (they still count as n_records) */
 } rdf_test_path_report;
 
 rdf_status rdf_test_paths(rdf_ctx* ctx, rdf_test_path_report* out);

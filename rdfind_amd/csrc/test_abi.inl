@@ -436,6 +436,8 @@ rdf_status rdf_test_paths(rdf_ctx* c, rdf_test_path_report* out) {
     r.sig_on = c->sig_on ? 1 : 0;
     r.piv2_on = c->piv2_on ? 1 : 0;
     r.k3_hist = c->k3_hist ? 1 : 0;
+    r.k3_key_items = c->k3_key_items;
+    r.k3_suppressed = c->k3_suppressed;
     r.hclassed = c->hclassed ? 1 : 0;
     r.n_emit_tiles = c->pend_NT;
     // the class lists as the run left them: class m's is lists[lwoff[cchoff[m]], lwoff[cchoff[m + 1]]).  n_classes and
