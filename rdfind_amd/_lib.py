@@ -61,7 +61,8 @@ RDF_NT_TABS = 1
 TEST_SYMBOLS = ("rdf_test_scan", "rdf_test_scan_batch", "rdf_test_radix", "rdf_test_radix_passes",
                 "rdf_test_radix_segments", "rdf_test_paths", "rdf_test_rewrite_form", "rdf_test_cind_stats_times",
                 "rdf_test_fc_trace", "rdf_test_fc_report", "rdf_test_copy_frequent_unary", "rdf_test_unary_lookup",
-                "rdf_test_record_tile", "rdf_test_keep_records", "rdf_test_group_build", "rdf_test_shard_report")
+                "rdf_test_record_tile", "rdf_test_keep_records", "rdf_test_group_build", "rdf_test_shard_report",
+                "rdf_test_radix_pairs", "rdf_test_group_kv")
 REWRITE_FORMS = {0: None, 1: "lds", 2: "global"}
 SCAN_U32_U32, SCAN_U32_U64, SCAN_U64_U64 = range(3)
 SCAN_DTYPES = {SCAN_U32_U32: (np.uint32, np.uint32), SCAN_U32_U64: (np.uint32, np.uint64),
@@ -70,6 +71,7 @@ RADIX_SORT_BITS, RADIX_SORT_DROP, RADIX_PART_HASHED, RADIX_PART_U32 = range(4)
 K1_FORMS = {0: None, 1: "partitioned", 2: "radix", 3: "atomic"}
 K2_FORMS = {0: None, 1: "plain", 2: "split", 3: "radix", 4: "atomic"}
 K3_FORMS = {0: None, 1: "onepass", 2: "twopass"}
+GROUP_FORMS = {0: None, 1: "u64", 2: "kv"}
 
 # rdf_exchange ops (sharded mode, include/rdfind_hip.h)
 X_DONE, X_ALLREDUCE_SUM_U32, X_ALLREDUCE_SUM_U64, X_ALLREDUCE_MIN_U64, X_ALLGATHERV_U64, X_ALLTOALLV_U64 = range(6)
@@ -130,7 +132,8 @@ class PathReport(ctypes.Structure):
                 ("piv2_on", ctypes.c_uint32), ("k3_hist", ctypes.c_uint32),
                 ("hclassed", ctypes.c_uint32), ("n_class_chunks", ctypes.c_uint64), ("n_emit_tiles", ctypes.c_uint64),
                 ("max_class_list", ctypes.c_uint64), ("n_multi_seg_lists", ctypes.c_uint64),
-                ("k3_key_items", ctypes.c_uint64), ("k3_suppressed", ctypes.c_uint64)]
+                ("k3_key_items", ctypes.c_uint64), ("k3_suppressed", ctypes.c_uint64),
+                ("group_form", ctypes.c_uint32)]
 
 
 class FcReport(ctypes.Structure):
@@ -346,6 +349,9 @@ def load():
         "rdf_test_keep_records": (i32, [P, P, u64, ctypes.c_int, u64, u32, P, ctypes.POINTER(u64), ctypes.POINTER(u32), P, P,
                                         P, ctypes.POINTER(u32)]),
         "rdf_test_group_build": (i32, [P, P, u64, u32, u64, u32, ctypes.POINTER(u64), P, P, P, ctypes.POINTER(u32)]),
+        "rdf_test_radix_pairs": (i32, [P, P, P, u64, ctypes.c_int, ctypes.c_int, P, P, ctypes.POINTER(u32)]),
+        "rdf_test_group_kv": (i32, [P, P, u64, ctypes.c_int, u64, u32, u32, P, ctypes.POINTER(u64), ctypes.POINTER(u32), P, P,
+                                    ctypes.POINTER(u64), P, P, P, ctypes.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None) if name in TEST_SYMBOLS else getattr(lib, name)
@@ -922,6 +928,39 @@ class Context:
         self._check(rc, "rdf_test_group_build")
         return goff[: g.value + 1], gcap[: a.shape[0]], gmap, bool(ok.value)
 
+    def test_radix_pairs(self, keys, vals, lo=0, hi=32):
+        """The stable pair sort of uint32 keys with uint32 values by key bits [lo, hi) (rdf_test_radix_pairs):
+        (sorted keys, their values, canaries_ok); canaries_ok also says that the uploaded keys and values are intact."""
+        k = np.ascontiguousarray(keys, dtype=np.uint32)
+        v = np.ascontiguousarray(vals, dtype=np.uint32)
+        assert k.shape == v.shape
+        ko, vo = np.empty_like(k), np.empty_like(v)
+        ok = ctypes.c_uint32()
+        rc = self._test_fn("rdf_test_radix_pairs")(self.ptr, k.ctypes.data, v.ctypes.data, k.shape[0], lo, hi,
+                                                   ko.ctypes.data, vo.ctypes.data, ctypes.byref(ok))
+        self.test_canaries_ok = bool(ok.value)
+        self._check(rc, "rdf_test_radix_pairs")
+        return ko, vo, bool(ok.value)
+
+    def test_group_kv(self, keys, joinbits: int, ncap: int, ms: int, num_values: int) -> dict:
+        """The key-value form of the one-pass group build over sorted records ``capture << joinbits | join``
+        (rdf_test_group_kv): support[ncap], doff[C + 1], dgrp[Jf], goff[G + 1], gcap[Jf], gmap[num_values], G, Jf and
+        canaries_ok, by name."""
+        a = np.ascontiguousarray(keys, dtype=np.uint64)
+        m = max(a.shape[0], 1)
+        sup, doff = np.empty(ncap, np.uint32), np.empty(ncap + 1, np.uint64)
+        dgrp, gcap = np.empty(m, np.uint32), np.empty(m, np.uint32)
+        goff, gmap = np.empty(m + 1, np.uint64), np.empty(num_values, np.uint32)
+        jf, g, ncomp, ok = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint32()
+        rc = self._test_fn("rdf_test_group_kv")(
+            self.ptr, a.ctypes.data, a.shape[0], joinbits, ncap, ms, num_values, sup.ctypes.data, ctypes.byref(jf),
+            ctypes.byref(ncomp), doff.ctypes.data, dgrp.ctypes.data, ctypes.byref(g), goff.ctypes.data, gcap.ctypes.data,
+            gmap.ctypes.data, ctypes.byref(ok))
+        self.test_canaries_ok = bool(ok.value)
+        self._check(rc, "rdf_test_group_kv")
+        return {"support": sup, "doff": doff[: ncomp.value + 1], "dgrp": dgrp[: jf.value], "goff": goff[: g.value + 1],
+                "gcap": gcap[: jf.value], "gmap": gmap, "G": g.value, "Jf": jf.value, "canaries_ok": bool(ok.value)}
+
     def test_paths(self) -> dict:
         """Which alternative paths the last completed run took (rdf_test_paths): the K1 / K2 / K3 forms by name,
         dense_on, light_stage, light_hiocc, n_dense, n_dense_eligible, n_dedup_members, and what the light launches
@@ -933,11 +972,13 @@ class Context:
         dependents read the class lists), n_class_chunks (k_class_eval work items), n_emit_tiles (k_class_emit tiles),
         max_class_list (refs of the longest L'(m)) and n_multi_seg_lists (lists longer than one emission segment).  Of K3's
         key items (RDFIND_EMIT_KEYS): k3_key_items (frequent binary keys the last build emitted from) and k3_suppressed
-        (records its triples left to them)."""
+        (records its triples left to them).  group_form: "kv" or "u64", the form of the last one-pass group build
+        (RDFIND_GROUP_KV); None after a build in join ranges."""
         r = PathReport()
         self._check(self._test_fn("rdf_test_paths")(self.ptr, ctypes.byref(r)), "rdf_test_paths")
         d = _struct_dict(r)
         d["k1_form"], d["k2_form"], d["k3_form"] = K1_FORMS[r.k1_form], K2_FORMS[r.k2_form], K3_FORMS[r.k3_form]
+        d["group_form"] = GROUP_FORMS[r.group_form]
         for name in ("dense_on", "light_stage", "light_hiocc", "light_ordered", "light_side", "light_two_pass", "sig_on",
                      "piv2_on", "k3_hist", "hclassed"):
             d[name] = bool(d[name])

@@ -1098,10 +1098,12 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_skip_counts(const u32* __restrict
 // and fk = (join << 32 | compact capture) at the same position (sorted by join next, for the groups).
 // One block per record tile: a record's fresh rank = tile_base[tile] (the scanned counts of k_fresh_bounds) + its
 // rank among the tile's fresh records.
-__global__ __launch_bounds__(RDF_BLOCK) void k_keep_scatter(const u64* __restrict__ keys, u64 n, int joinbits,
-                                                            const u32* __restrict__ tile_base, const u32* __restrict__ skip,
-                                                            const u32* __restrict__ support, u32 ms,
-                                                            const u32* __restrict__ fidx, u64* dk, u64* fk) {
+// KV: the 4-byte form, joins[p] = join and caps[p] = compact capture (dk's and fk's low halves) instead of dk and fk.
+template <bool KV>
+__device__ inline void keep_scatter_body(const u64* __restrict__ keys, u64 n, int joinbits,
+                                         const u32* __restrict__ tile_base, const u32* __restrict__ skip,
+                                         const u32* __restrict__ support, u32 ms, const u32* __restrict__ fidx, u64* dk,
+                                         u64* fk, u32* joins, u32* caps) {
     __shared__ u32 s_off[KT_SEG], s_total;
     const u64 jmask = (1ull << joinbits) - 1;
     const u64 base = (u64)blockIdx.x * KT_TILE;
@@ -1128,22 +1130,45 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_keep_scatter(const u64* __restric
         if (support[cap] < ms) continue;
         const u64 p = tb + s_off[kt_seg(u)] + (u32)__popcll(fb[u] & lt) - skip[cap];
         const u64 c = fidx[cap], j = k[u] & jmask;
-        dk[p] = (c << 32) | j;
-        fk[p] = (j << 32) | c;
+        if (KV) {
+            joins[p] = (u32)j;
+            caps[p] = (u32)c;
+        } else {
+            dk[p] = (c << 32) | j;
+            fk[p] = (j << 32) | c;
+        }
     }
+}
+__global__ __launch_bounds__(RDF_BLOCK) void k_keep_scatter(const u64* __restrict__ keys, u64 n, int joinbits,
+                                                            const u32* __restrict__ tile_base, const u32* __restrict__ skip,
+                                                            const u32* __restrict__ support, u32 ms,
+                                                            const u32* __restrict__ fidx, u64* dk, u64* fk) {
+    keep_scatter_body<false>(keys, n, joinbits, tile_base, skip, support, ms, fidx, dk, fk, nullptr, nullptr);
+}
+__global__ __launch_bounds__(RDF_BLOCK) void k_keep_scatter_kv(const u64* __restrict__ keys, u64 n, int joinbits,
+                                                               const u32* __restrict__ tile_base,
+                                                               const u32* __restrict__ skip,
+                                                               const u32* __restrict__ support, u32 ms,
+                                                               const u32* __restrict__ fidx, u32* joins, u32* caps) {
+    keep_scatter_body<true>(keys, n, joinbits, tile_base, skip, support, ms, fidx, nullptr, nullptr, joins, caps);
 }
 
 // group heads of the join-sorted fk = (join << 32 | capture): records whose join value differs from the predecessor's.
 // The counting pass: tile_heads[t] = heads of record tile t.
-__global__ __launch_bounds__(RDF_BLOCK) void k_group_flags(const u64* __restrict__ fk, u64 n, u32* tile_heads) {
+// A join-sorted record's join value: the high half of fk, or the record itself where the sorted joins are an array
+// of their own (the key-value group sort).
+__device__ inline u32 rec_join(u64 r) { return (u32)(r >> 32); }
+__device__ inline u32 rec_join(u32 r) { return r; }
+template <typename RT>
+__device__ inline void group_flags_body(const RT* __restrict__ fk, u64 n, u32* tile_heads) {
     __shared__ u32 s_w[RDF_WAVES_PER_BLOCK];
     const u64 base = (u64)blockIdx.x * KT_TILE;
     u32 a[KT_U], b[KT_U];
 #pragma unroll
     for (int u = 0; u < KT_U; ++u) {
         const u64 i = base + (u64)u * RDF_BLOCK + threadIdx.x;
-        a[u] = i < n ? (u32)(fk[i] >> 32) : 0u;
-        b[u] = i && i < n ? (u32)(fk[i - 1] >> 32) : 0u;
+        a[u] = i < n ? rec_join(fk[i]) : 0u;
+        b[u] = i && i < n ? rec_join(fk[i - 1]) : 0u;
     }
     u32 cnt = 0;  // (the same in every lane of the wave)
 #pragma unroll
@@ -1160,26 +1185,35 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_group_flags(const u64* __restrict
         tile_heads[blockIdx.x] = t;
     }
 }
+__global__ __launch_bounds__(RDF_BLOCK) void k_group_flags(const u64* __restrict__ fk, u64 n, u32* tile_heads) {
+    group_flags_body(fk, n, tile_heads);
+}
+__global__ __launch_bounds__(RDF_BLOCK) void k_group_flags_kv(const u32* __restrict__ sj, u64 n, u32* tile_heads) {
+    group_flags_body(sj, n, tile_heads);
+}
 
 // groups: goff[gbase + g] = rbase + first record; gcap[rbase + i] = compact capture id; gmap[join] = gbase + g.
 // The writing pass: a head's group = tile_gbase[tile] (the scanned counts of k_group_flags) + its rank among the tile's
 // heads.
-__device__ inline void group_build_body(const u64* __restrict__ fk, u64 n, const u32* __restrict__ tile_gbase, u64 rbase,
+// RT = u32: the records are the sorted joins alone and gcap is not written (the key-value group sort's last pass wrote it).
+template <typename RT>
+__device__ inline void group_build_body(const RT* __restrict__ fk, u64 n, const u32* __restrict__ tile_gbase, u64 rbase,
                                         u32 gbase, u64* goff, u32* gcap, u32* gmap) {
     __shared__ u32 s_off[KT_SEG], s_total;
     const u64 base = (u64)blockIdx.x * KT_TILE;
-    u64 k[KT_U], hb[KT_U];
+    RT k[KT_U];
+    u64 hb[KT_U];
     u32 b[KT_U];
 #pragma unroll
     for (int u = 0; u < KT_U; ++u) {
         const u64 i = base + (u64)u * RDF_BLOCK + threadIdx.x;
-        k[u] = i < n ? fk[i] : 0ull;
-        b[u] = i && i < n ? (u32)(fk[i - 1] >> 32) : 0u;
+        k[u] = i < n ? fk[i] : (RT)0;
+        b[u] = i && i < n ? rec_join(fk[i - 1]) : 0u;
     }
 #pragma unroll
     for (int u = 0; u < KT_U; ++u) {
         const u64 i = base + (u64)u * RDF_BLOCK + threadIdx.x;
-        hb[u] = __ballot(i < n && (i == 0 || (u32)(k[u] >> 32) != b[u]));
+        hb[u] = __ballot(i < n && (i == 0 || rec_join(k[u]) != b[u]));
     }
     tile_seg_scan(hb, s_off, &s_total);
     const u32 g0 = gbase + tile_gbase[blockIdx.x];
@@ -1189,11 +1223,11 @@ __device__ inline void group_build_body(const u64* __restrict__ fk, u64 n, const
     for (int u = 0; u < KT_U; ++u) {
         const u64 i = base + (u64)u * RDF_BLOCK + threadIdx.x;
         if (i >= n) break;
-        gcap[rbase + i] = (u32)(k[u] & 0xffffffffu);
+        if (sizeof(RT) == 8) gcap[rbase + i] = (u32)((u64)k[u] & 0xffffffffu);
         if ((hb[u] >> lane) & 1ull) {
             const u32 g = g0 + s_off[kt_seg(u)] + (u32)__popcll(hb[u] & lt);
             goff[g] = rbase + i;
-            gmap[k[u] >> 32] = g;
+            gmap[rec_join(k[u])] = g;
         }
     }
 }
@@ -1202,10 +1236,16 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_group_build(const u64* __restrict
                                                            u32* gmap) {
     group_build_body(fk, n, tile_gbase, 0, 0u, goff, gcap, gmap);
 }
+__global__ __launch_bounds__(RDF_BLOCK) void k_group_build_kv(const u32* __restrict__ sj, u64 n,
+                                                              const u32* __restrict__ tile_gbase, u64* goff, u32* gmap) {
+    group_build_body(sj, n, tile_gbase, 0, 0u, goff, nullptr, gmap);
+}
 
 // dependent -> groups: dgrp[i] = group of the join value of dk[i].  A capture's joins ascend and group ids
 // are assigned in join order, so every dependent's group list comes out sorted.
-__global__ __launch_bounds__(RDF_BLOCK) void k_dgrp(const u64* __restrict__ dk, u64 n, const u32* __restrict__ gmap, u32* dgrp) {
+// RT = u32: dk's low halves as an array of their own (the joins k_keep_scatter_kv wrote).
+template <typename RT>
+__device__ inline void dgrp_body(const RT* __restrict__ dk, u64 n, const u32* __restrict__ gmap, u32* dgrp) {
     const u64 T = (u64)gridDim.x * RDF_BLOCK;
     for (u64 i0 = (u64)blockIdx.x * RDF_BLOCK + threadIdx.x; i0 < n; i0 += T * STREAM_U) {
         u32 j[STREAM_U], g[STREAM_U];
@@ -1217,6 +1257,13 @@ __global__ __launch_bounds__(RDF_BLOCK) void k_dgrp(const u64* __restrict__ dk, 
         for (int u = 0; u < STREAM_U; ++u)
             if (i0 + (u64)u * T < n) dgrp[i0 + (u64)u * T] = g[u];
     }
+}
+__global__ __launch_bounds__(RDF_BLOCK) void k_dgrp(const u64* __restrict__ dk, u64 n, const u32* __restrict__ gmap, u32* dgrp) {
+    dgrp_body(dk, n, gmap, dgrp);
+}
+__global__ __launch_bounds__(RDF_BLOCK) void k_dgrp_kv(const u32* __restrict__ joins, u64 n, const u32* __restrict__ gmap,
+                                                       u32* dgrp) {
+    dgrp_body(joins, n, gmap, dgrp);
 }
 
 __global__ __launch_bounds__(RDF_BLOCK) void k_info_support_u32(const CapInfo* __restrict__ info, u32 C, u32* out) {

@@ -1039,4 +1039,226 @@ hipError_t radix_partition_u32(Workspace& ws, u32*& keys, u32*& tmp, u64 n, int 
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Stable key-value sort of u32 keys with u32 values (the group build's joins and captures): the passes of the key
+// sorts above (count, k_radix_rowscan, tile scatter; RS_TILE keys per tile, rs_tile() numbering), with the pairs held
+// as two arrays so that a pass which only looks at keys reads 4 bytes per pair.
+
+// a tile's elements in 16-byte loads: row r of lane t holds elements tbase + 4 (r RDF_BLOCK + t) + 0..3; elements at or
+// past n read as 0.  a is 16-byte aligned.
+__device__ inline void load_tile_quads(const u32* __restrict__ a, u64 n, u64 tbase, u32 (&k)[RS_ITEMS]) {
+    static_assert(RS_ITEMS % 4 == 0, "a lane loads whole quads");
+#pragma unroll
+    for (int r = 0; r < RS_ITEMS / 4; ++r) {
+        const u64 idx = tbase + 4ull * ((u64)r * RDF_BLOCK + threadIdx.x);
+        if (idx + 3 < n) {
+            const u32x4_t v = *(const u32x4_t*)(a + idx);
+            k[4 * r] = v.x;
+            k[4 * r + 1] = v.y;
+            k[4 * r + 2] = v.z;
+            k[4 * r + 3] = v.w;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) k[4 * r + q] = idx + q < n ? a[idx + q] : 0u;
+        }
+    }
+}
+
+// the count pass of a pair sort: k_radix_count on the key array alone, four keys a load
+template <int DB>
+__global__ __launch_bounds__(RDF_BLOCK) void k_radix_count_kv(const u32* __restrict__ keys, u64 n, int shift, int w,
+                                                              u32* __restrict__ hist, u32 num_tiles) {
+    constexpr u32 NBIN = 1u << DB;
+    __shared__ u32 wcnt[RDF_WAVES_PER_BLOCK][NBIN];
+    const int lane = lane_id();
+    const int wave = threadIdx.x / RDF_WAVE;
+    const u32 dmask = (1u << w) - 1u;
+    for (u32 i = threadIdx.x; i < RDF_WAVES_PER_BLOCK * NBIN; i += RDF_BLOCK) (&wcnt[0][0])[i] = 0;
+    __syncthreads();
+    const u32 tile = rs_tile();
+    const u64 tbase = (u64)tile * RS_TILE;
+    u32 k[RS_ITEMS];
+    load_tile_quads(keys, n, tbase, k);  // counting is order-free: any assignment of keys to lanes works
+#pragma unroll
+    for (int r = 0; r < RS_ITEMS; ++r) {
+        const bool valid = tbase + 4ull * ((u64)(r / 4) * RDF_BLOCK + threadIdx.x) + (r & 3) < n;
+        const u32 d = (k[r] >> shift) & dmask;
+        const u64 peers = digit_peers<DB>(d, valid);
+        if (valid && ((peers >> lane) >> 1) == 0) wcnt[wave][d] += (u32)__popcll(peers);
+    }
+    __syncthreads();
+    for (u32 b = threadIdx.x; b <= dmask; b += RDF_BLOCK) {
+        u32 sum = 0;
+#pragma unroll
+        for (int ww = 0; ww < RDF_WAVES_PER_BLOCK; ++ww) sum += wcnt[ww][b];
+        hist[(u64)b * num_tiles + tile] = sum;
+    }
+}
+
+// the scatter pass of a pair sort: the keys ranked as k_radix_scatter ranks them, keys and values reordered by digit in
+// LDS (2 x RS_TILE x 4 B, what RS_TILE u64 keys take) and both written out as per-digit runs
+template <int DB>
+__global__ __launch_bounds__(RDF_BLOCK) void k_radix_scatter_kv(const u32* __restrict__ keys, const u32* __restrict__ vals,
+                                                                u32* __restrict__ okeys, u32* __restrict__ ovals, u64 n,
+                                                                int shift, int w, const u32* __restrict__ offs,
+                                                                const u32* __restrict__ rowtot, u32 num_tiles) {
+    constexpr u32 NBIN = 1u << DB;
+    constexpr u32 PER = NBIN / RDF_BLOCK;  // digits per thread in the tile scan (1, 2 or 4)
+    static_assert(NBIN % RDF_BLOCK == 0, "digit bins must be a multiple of the block");
+    __shared__ __align__(16) u32 skeys[RS_TILE];
+    __shared__ __align__(16) u32 svals[RS_TILE];
+    __shared__ u32 wcount[RDF_WAVES_PER_BLOCK][NBIN];
+    __shared__ u32 tstart[NBIN];
+    __shared__ u32 gbase[NBIN];
+    __shared__ u32 lds_wave[RDF_WAVES_PER_BLOCK];
+    const int lane = lane_id();
+    const int wave = threadIdx.x / RDF_WAVE;
+    const u32 nbin = 1u << w, dmask = nbin - 1u;
+    for (u32 i = threadIdx.x; i < RDF_WAVES_PER_BLOCK * NBIN; i += RDF_BLOCK) (&wcount[0][0])[i] = 0;
+    const u32 tile = rs_tile();
+    const u64 tbase = (u64)tile * RS_TILE;
+    const u32 tn = n - tbase < (u64)RS_TILE ? (u32)(n - tbase) : (u32)RS_TILE;
+    {   // stage the tile's keys and values through LDS (16-byte loads; each wave then reads its contiguous sub-range);
+        // while they are in flight, the digits' bases as in k_radix_scatter
+        u32 kin[RS_ITEMS], vin[RS_ITEMS];
+        load_tile_quads(keys, n, tbase, kin);
+        load_tile_quads(vals, n, tbase, vin);
+        u32 rt[PER], ro[PER], local = 0;
+#pragma unroll
+        for (u32 q = 0; q < PER; ++q) {
+            const u32 dg = threadIdx.x * PER + q;
+            rt[q] = dg < nbin ? rowtot[dg] : 0u;
+            ro[q] = dg < nbin ? offs[(u64)dg * num_tiles + tile] : 0u;
+            local += rt[q];
+        }
+        u32 total;
+        u32 off = block_exclusive_scan<u32>(local, lds_wave, &total);
+#pragma unroll
+        for (u32 q = 0; q < PER; ++q) {
+            gbase[threadIdx.x * PER + q] = off + ro[q];
+            off += rt[q];
+        }
+#pragma unroll
+        for (int r = 0; r < RS_ITEMS / 4; ++r) {
+            const u32 p = 4u * ((u32)r * RDF_BLOCK + threadIdx.x);
+            *(u32x4_t*)(skeys + p) = u32x4_t{kin[4 * r], kin[4 * r + 1], kin[4 * r + 2], kin[4 * r + 3]};
+            *(u32x4_t*)(svals + p) = u32x4_t{vin[4 * r], vin[4 * r + 1], vin[4 * r + 2], vin[4 * r + 3]};
+        }
+    }
+    __syncthreads();
+    u32 k[RS_ITEMS], v[RS_ITEMS], rank[RS_ITEMS];
+    const u64 lt = lanemask_lt();
+    const u32 wofs = (u32)wave * RS_WAVE_KEYS;
+#pragma unroll
+    for (int r = 0; r < RS_ITEMS; ++r) {
+        k[r] = skeys[wofs + (u32)r * RDF_WAVE + lane];
+        v[r] = svals[wofs + (u32)r * RDF_WAVE + lane];
+    }
+#pragma unroll
+    for (int r = 0; r < RS_ITEMS; ++r) {
+        const bool valid = wofs + (u32)r * RDF_WAVE + lane < tn;
+        const u32 d = (k[r] >> shift) & dmask;
+        const u64 peers = digit_peers<DB>(d, valid);
+        const u32 before = (u32)__popcll(peers & lt);
+        const u32 old = valid ? wcount[wave][d] : 0;
+        // the highest peer lane publishes the new running count (reads above precede this write)
+        if (valid && ((peers >> lane) >> 1) == 0) wcount[wave][d] = old + before + 1;
+        rank[r] = old + before;
+    }
+    __syncthreads();
+    {   // exclusive prefix over waves per digit, then over digits for the tile (PER consecutive digits a thread)
+        u32 run[PER], local = 0;
+#pragma unroll
+        for (u32 q = 0; q < PER; ++q) {
+            const u32 dg = threadIdx.x * PER + q;
+            u32 acc = 0;
+#pragma unroll
+            for (int ww = 0; ww < RDF_WAVES_PER_BLOCK; ++ww) {
+                const u32 c = wcount[ww][dg];
+                wcount[ww][dg] = acc;
+                acc += c;
+            }
+            run[q] = acc;
+            local += acc;
+        }
+        u32 total;
+        u32 off = block_exclusive_scan<u32>(local, lds_wave, &total);
+#pragma unroll
+        for (u32 q = 0; q < PER; ++q) {
+            tstart[threadIdx.x * PER + q] = off;
+            off += run[q];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < RS_ITEMS; ++r) {
+        if (wofs + (u32)r * RDF_WAVE + lane < tn) {
+            const u32 d = (k[r] >> shift) & dmask;
+            const u32 p = tstart[d] + wcount[wave][d] + rank[r];
+            skeys[p] = k[r];
+            svals[p] = v[r];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < RS_ITEMS; ++i) {
+        const u32 p = (u32)i * RDF_BLOCK + threadIdx.x;
+        if (p < tn) {
+            const u32 key = skeys[p];
+            const u32 d = (key >> shift) & dmask;
+            const u64 at = (u64)gbase[d] + (p - tstart[d]);
+            okeys[at] = key;
+            ovals[at] = svals[p];
+        }
+    }
+}
+
+template <int DB>
+static hipError_t radix_pass_kv(Workspace& ws, const u32* keys, const u32* vals, u32* okeys, u32* ovals, u64 n, int shift,
+                                int w, u32* hist, u32 tiles, hipStream_t st) {
+    u32* rowtot = (u32*)ws.scratch(1024 * sizeof(u32), 2);
+    if (!rowtot) return hipErrorOutOfMemory;
+    const u32 rs = hist_stride(tiles);
+    hipLaunchKernelGGL(k_radix_count_kv<DB>, dim3(tiles), dim3(RDF_BLOCK), 0, st, keys, n, shift, w, hist, rs);
+    hipLaunchKernelGGL(k_radix_rowscan, dim3(1u << w), dim3(RS_SCAN_THREADS), 0, st, hist, rs, tiles, rowtot);
+    hipLaunchKernelGGL(k_radix_scatter_kv<DB>, dim3(tiles), dim3(RDF_BLOCK), 0, st, keys, vals, okeys, ovals, n, shift, w, hist,
+                       rowtot, rs);
+    return hipGetLastError();
+}
+
+// Pass p of P reads what pass p - 1 wrote (pass 0: the input) and writes the out arrays when P - 1 - p is even, the tmp
+// arrays otherwise: the last pass ends in (keys_out, vals_out) and no pass writes the input, whatever P is.
+hipError_t radix_sort_pairs_u32(Workspace& ws, const u32* keys_in, const u32* vals_in, u32* keys_out, u32* vals_out,
+                                u32* keys_tmp, u32* vals_tmp, u64 n, int lo, int hi, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    if (n >= (1ull << 32) || lo < 0 || hi > 32) return hipErrorInvalidValue;
+    for (const u32* a : {keys_in, vals_in, (const u32*)keys_out, (const u32*)vals_out, (const u32*)keys_tmp, (const u32*)vals_tmp})
+        if (!a || ((uintptr_t)a & 15u)) return hipErrorInvalidValue;
+    const int bits = hi - lo, dmax = sort_digit_bits(bits);
+    const int passes = n < 2 || bits <= 0 ? 0 : (bits + dmax - 1) / dmax;
+    if (passes == 0) {  // nothing to order: the output is the input
+        hipError_t e = hipMemcpyAsync(keys_out, keys_in, n * 4, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(vals_out, vals_in, n * 4, hipMemcpyDeviceToDevice, st);
+        return e;
+    }
+    const u32 tiles = (u32)((n + RS_TILE - 1) / RS_TILE);
+    u32* hist = (u32*)ws.scratch(((u64)hist_stride(tiles) << dmax) * sizeof(u32), 1);
+    if (!hist) return hipErrorOutOfMemory;
+    const u32 *sk = keys_in, *sv = vals_in;
+    int shift = lo;
+    for (int p = 0; p < passes; ++p) {
+        const int w = bits / passes + (p < bits % passes ? 1 : 0);  // the wider digits first
+        const bool to_out = ((passes - 1 - p) & 1) == 0;
+        u32 *dk = to_out ? keys_out : keys_tmp, *dv = to_out ? vals_out : vals_tmp;
+        hipError_t e = w <= 8 ? radix_pass_kv<8>(ws, sk, sv, dk, dv, n, shift, w, hist, tiles, st)
+                     : w == 9 ? radix_pass_kv<9>(ws, sk, sv, dk, dv, n, shift, w, hist, tiles, st)
+                              : radix_pass_kv<10>(ws, sk, sv, dk, dv, n, shift, w, hist, tiles, st);
+        if (e != hipSuccess) return e;
+        sk = dk;
+        sv = dv;
+        shift += w;
+    }
+    return hipGetLastError();
+}
+
 }  // namespace rdf

@@ -115,5 +115,10 @@ int radix_sort_passes(int bits);  // passes of a sort of `bits` key bits
 hipError_t radix_partition_hashed(Workspace& ws, u64*& keys, u64*& tmp, u64 n, int bits, u64 hmask, hipStream_t st);
 // u32 keys ordered by bits [lo, hi) (stable LSD passes of <= 8 bits); keys / tmp swap so that `keys` holds the result
 hipError_t radix_partition_u32(Workspace& ws, u32*& keys, u32*& tmp, u64 n, int lo, int hi, hipStream_t st);
+// Stable sort of n (key, value) pairs of u32 by key bits [lo, hi), digits as radix_sort_u64_bits takes them: the pairs end
+// in (keys_out, vals_out); (keys_in, vals_in) are only read and (keys_tmp, vals_tmp) are scratch of n elements each (not
+// touched by a single pass).  All six arrays are distinct and 16-byte aligned.  Uses workspace slots 1 and 2.
+hipError_t radix_sort_pairs_u32(Workspace& ws, const u32* keys_in, const u32* vals_in, u32* keys_out, u32* vals_out,
+                                u32* keys_tmp, u32* vals_tmp, u64 n, int lo, int hi, hipStream_t st);
 
 }  // namespace rdf

@@ -302,7 +302,7 @@ struct rdf_ctx : CtxBuffers {
     bool dense_flagged = false;           // d_dense_flags numbered rows this run (d_dense_build fills them)
     u64 n_dense_eligible = 0;             // groups d_dense_flags numbered (n_dense: the rows d_dense_build gave a bitmap)
     // which alternative ran at the run's decision points (RDF_TEST_K1_* / K2_* / K3_*, test_abi.h; 0: none yet)
-    u32 path_k1 = 0, path_k2 = 0, path_k3 = 0;
+    u32 path_k1 = 0, path_k2 = 0, path_k3 = 0, path_group_kv = 0;
     // rdf_test_fc_trace / rdf_test_fc_report (test_abi.h): the shape of the last frequent-condition stage; with fc_trace
     // on, the stage also reads its slice lists back (fc_trace_slices)
     bool fc_trace = false;
@@ -2123,6 +2123,7 @@ static rdf_status g_record_bits(rdf_ctx* c) {
     c->dense_on = false;
     c->n_dense = c->n_dense_eligible = c->n_dedup_members = 0;
     c->path_k3 = 0;
+    c->path_group_kv = 0;
     c->k3_hist = false;
     c->k3_key_items = c->k3_suppressed = 0;
     const u32 V = c->V ? c->V : 1;
@@ -2442,14 +2443,15 @@ static rdf_status g_compact_captures(rdf_ctx* c) {
     return RDF_OK;
 }
 
-// group heads of Jr join-sorted kept records (c->fk): the heads per record tile (c->tile_heads), their scan
-// (c->tile_gbase) and the number of groups -> *Gout (one read-back)
-static rdf_status g_group_heads(rdf_ctx* c, u64 Jr, u32* Gout) {
+// group heads of Jr join-sorted kept records (c->fk; sj: the sorted joins of the key-value form instead): the heads per
+// record tile (c->tile_heads), their scan (c->tile_gbase) and the number of groups -> *Gout (one read-back)
+static rdf_status g_group_heads(rdf_ctx* c, u64 Jr, const u32* sj, u32* Gout) {
     hipStream_t st = c->stream;
     const unsigned nt = rec_tiles(Jr);
     ENSURE(c, tile_heads, std::max<u64>(nt, 1) * 4);
     ENSURE(c, tile_gbase, (nt + 1ull) * 4);
-    if (nt) hipLaunchKernelGGL(k_group_flags, dim3(nt), dim3(RDF_BLOCK), 0, st, c->fk.as<u64>(), Jr, c->tile_heads.as<u32>());
+    if (nt && sj) hipLaunchKernelGGL(k_group_flags_kv, dim3(nt), dim3(RDF_BLOCK), 0, st, sj, Jr, c->tile_heads.as<u32>());
+    else if (nt) hipLaunchKernelGGL(k_group_flags, dim3(nt), dim3(RDF_BLOCK), 0, st, c->fk.as<u64>(), Jr, c->tile_heads.as<u32>());
     HIP_TRY(c, exclusive_scan_u32(c->ws, c->tile_heads.as<u32>(), c->tile_gbase.as<u32>(), nt, c->tile_gbase.as<u32>() + nt, st));
     return read_u32(c, c->tile_gbase.as<u32>() + nt, Gout);
 }
@@ -2478,10 +2480,26 @@ static rdf_status g_compact_groups(rdf_ctx* c, const u32* local_sup) {
     TRY(read_multi(c, {{c->tile_base.as<u32>() + nt, 4}, {c->skip.as<u32>() + ncap, 4}}, fs));
     const u64 Jf = fs[0] - fs[1];
     c->Jf = Jf;
-    u64* dk = keys == c->rec.as<u64>() ? c->rec_tmp.as<u64>() : c->rec.as<u64>();
-    ENSURE(c, fk, std::max<u64>(Jf, 1) * 8);
-    ENSURE(c, fk_tmp, std::max<u64>(Jf, 1) * 8);
-    if (nt)
+    // The record buffer that does not hold the sorted keys takes the kept records.  The key-value form (group_kv) keeps
+    // them as two u32 arrays there, joins and caps (dk's and fk's low halves; Jq: Jf rounded up to whole 16-byte quads),
+    // and needs no fk / fk_tmp: once the keep pass has read the sorted keys, their buffer is the pair sort's scratch.
+    const bool kv = c->sw.group_kv;
+    c->path_group_kv = kv ? RDF_TEST_GROUPS_KV : RDF_TEST_GROUPS_U64;
+    const bool keys_in_rec = keys == c->rec.as<u64>();
+    DevBuf& kept = keys_in_rec ? c->rec_tmp : c->rec;
+    const u64 Jq = (Jf + 3) & ~3ull;
+    if (kv) {
+        TRY(ensure_buf(c, &kept, std::max<u64>(Jq, 4) * 8, "allocating the kept joins and captures"));
+    } else {
+        ENSURE(c, fk, std::max<u64>(Jf, 1) * 8);
+        ENSURE(c, fk_tmp, std::max<u64>(Jf, 1) * 8);
+    }
+    u64* dk = kept.as<u64>();
+    u32 *joins = kept.as<u32>(), *caps = kept.as<u32>() + Jq;
+    if (nt && kv)
+        hipLaunchKernelGGL(k_keep_scatter_kv, dim3(nt), dim3(RDF_BLOCK), 0, st, keys, J, joinbits, c->tile_base.as<u32>(),
+                           c->skip.as<u32>(), c->support.as<u32>(), c->ms, c->fidx.as<u32>(), joins, caps);
+    else if (nt)
         hipLaunchKernelGGL(k_keep_scatter, dim3(nt), dim3(RDF_BLOCK), 0, st, keys, J, joinbits, c->tile_base.as<u32>(),
                            c->skip.as<u32>(), c->support.as<u32>(), c->ms, c->fidx.as<u32>(), dk, c->fk.as<u64>());
     tend(c, RDF_T_SUPPORT);
@@ -2504,20 +2522,33 @@ static rdf_status g_compact_groups(rdf_ctx* c, const u32* local_sup) {
         nrec = c->dcur.as<u32>();
     }
     HIP_TRY(c, exclusive_scan_u32_u64(c->ws, nrec, c->doff.as<u64>(), C, c->doff.as<u64>() + C, st));
-    if (Jf) {
+    // the key-value form sorts (joins, caps) by join: the sorted captures are gcap itself, and the sorted joins, read by the
+    // two group passes only, lie in dgrp until k_dgrp (the last launch here) writes the group lists over them
+    const u32* sj = c->dgrp.as<u32>();
+    ENSURE(c, gcap, std::max<u64>(Jf, 1) * 4 + 16);  // + 16 B: the light pass reads whole aligned quads
+    if (Jf && kv) {
+        DevBuf& spent = keys_in_rec ? c->rec : c->rec_tmp;  // the sorted keys: read for the last time by the keep pass
+        TRY(ensure_buf(c, &spent, Jq * 8, "allocating the pair sort's scratch"));
+        HIP_TRY(c, radix_sort_pairs_u32(c->ws, joins, caps, c->dgrp.as<u32>(), c->gcap.as<u32>(), spent.as<u32>(),
+                                        spent.as<u32>() + Jq, Jf, 0, joinbits, st));
+    } else if (Jf) {
         u64* tk = c->fk.as<u64>();
         u64* tt = c->fk_tmp.as<u64>();
         HIP_TRY(c, radix_sort_u64_bits(c->ws, tk, tt, Jf, 32, 32 + joinbits, st));
         if (tk != c->fk.as<u64>()) std::swap(c->fk, c->fk_tmp);
     }
     u32 G32 = 0;
-    TRY(g_group_heads(c, Jf, &G32));
+    TRY(g_group_heads(c, Jf, kv ? sj : nullptr, &G32));
     const u64 G = G32;
     c->G = G;
     ENSURE(c, goff, (G + 1) * 8);
-    ENSURE(c, gcap, std::max<u64>(Jf, 1) * 4 + 16);  // + 16 B: the light pass reads whole aligned quads
     ENSURE(c, gmap, (u64)V * 4);
-    if (Jf) {
+    if (Jf && kv) {
+        hipLaunchKernelGGL(k_group_build_kv, dim3(rec_tiles(Jf)), dim3(RDF_BLOCK), 0, st, sj, Jf, c->tile_gbase.as<u32>(),
+                           c->goff.as<u64>(), c->gmap.as<u32>());
+        hipLaunchKernelGGL(k_dgrp_kv, dim3(grid_for(Jf, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, joins, Jf,
+                           c->gmap.as<u32>(), c->dgrp.as<u32>());
+    } else if (Jf) {
         hipLaunchKernelGGL(k_group_build, dim3(rec_tiles(Jf)), dim3(RDF_BLOCK), 0, st, c->fk.as<u64>(), Jf,
                            c->tile_gbase.as<u32>(), c->goff.as<u64>(), c->gcap.as<u32>(), c->gmap.as<u32>());
         hipLaunchKernelGGL(k_dgrp, dim3(grid_for(Jf, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, dk, Jf, c->gmap.as<u32>(),
@@ -2832,7 +2863,7 @@ static rdf_status g_ranges_groups(rdf_ctx* c, int proj, JoinSel own, const u32* 
             if (tk != c->fk.as<u64>()) std::swap(c->fk, c->fk_tmp);
         }
         u32 Gr = 0;
-        TRY(g_group_heads(c, Jr, &Gr));
+        TRY(g_group_heads(c, Jr, nullptr, &Gr));
         if (G0 + Gr > Gmax || Jf0 + Jr > Jf) return fail(c, RDF_ERR_LIMIT, "join ranges disagree on the kept records");
         if (Jr) {
             hipLaunchKernelGGL(k_group_build_at, dim3(rec_tiles(Jr)), dim3(RDF_BLOCK), 0, st, c->fk.as<u64>(), Jr,

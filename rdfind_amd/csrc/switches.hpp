@@ -71,6 +71,8 @@ static inline RankPhase rank_phase(const char* v) {  // "rank:phase"; anything e
        "0: K3 has no key items: every triple writes the two unary records its frequent binary keys determine") \
     SW(emit_grid, u64, 0, "RDFIND_EMIT_GRID", strtoull(v, nullptr, 10), TEST, \
        "=<blocks>: cap of K3's emission grid (small: a small input's blocks emit regions of several sort sub-tiles)") \
+    SW(group_kv, bool, true, "RDFIND_GROUP_KV", atoi(v) != 0, AB, \
+       "0: the one-pass group build keeps and sorts its records as u64 (dk, fk), not as u32 joins and captures") \
     /* cinds: the pivot pass and the light passes */ \
     SW(allow_hclass, bool, true, "RDFIND_HCLASS", strcmp(v, "0") != 0, AB, \
        "=0: binary heavy-only dependents are not emitted from class lists") \

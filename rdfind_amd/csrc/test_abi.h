@@ -96,11 +96,30 @@ rdf_status rdf_test_group_build(rdf_ctx* ctx, const uint64_t* fk_host, uint64_t 
                                 uint32_t gbase, uint64_t* G_out, uint64_t* goff_out, uint32_t* gcap_out, uint32_t* gmap_out,
                                 uint32_t* canaries_ok);
 
+/* radix_sort_pairs_u32 on caller data: the n pairs (keys_host[i], vals_host[i]) stably sorted by key bits [lo, hi) into
+ * keys_out / vals_out (n entries each).  The six device arrays lie between canaries; *canaries_ok also says that the input
+ * keys and values still hold what was uploaded and that a sort of a single pass left the scratch arrays alone. */
+rdf_status rdf_test_radix_pairs(rdf_ctx* ctx, const uint32_t* keys_host, const uint32_t* vals_host, uint64_t n, int lo,
+                                int hi, uint32_t* keys_out, uint32_t* vals_out, uint32_t* canaries_ok);
+
+/* The key-value form of the one-pass group build (g_compact_groups under RDFIND_GROUP_KV: k_fresh_bounds,
+ * k_keep_scatter_kv, radix_sort_pairs_u32, k_group_flags_kv, k_group_build_kv, k_dgrp_kv) over n sorted records keys_host[i]
+ * = capture << joinbits | join as rdf_test_keep_records takes them, join < V <= 2^joinbits.  support_out[0, ncap), *C_out,
+ * *Jf_out and doff_out[0, C] as there; dgrp_out[0, Jf) = the group of every kept record in (capture, join) order; *G_out,
+ * goff_out[0, G] (goff_out[G] = Jf), gcap_out[0, Jf) and gmap_out[0, V) as rdf_test_group_build gives them with rbase =
+ * gbase = 0.  dgrp_out and gcap_out hold n entries, goff_out n + 1, doff_out ncap + 1.  The sorted joins live in the dgrp
+ * array until k_dgrp_kv overwrites them, as in the pipeline. */
+rdf_status rdf_test_group_kv(rdf_ctx* ctx, const uint64_t* keys_host, uint64_t n, int joinbits, uint64_t ncap, uint32_t ms,
+                             uint32_t V, uint32_t* support_out, uint64_t* Jf_out, uint32_t* C_out, uint64_t* doff_out,
+                             uint32_t* dgrp_out, uint64_t* G_out, uint64_t* goff_out, uint32_t* gcap_out,
+                             uint32_t* gmap_out, uint32_t* canaries_ok);
+
 /* Paths of the last completed run (RDF_ERR_STATE without one).  0 in a form field: that stage made no choice
  * (K2 and K3 of an input without triples). */
 enum { RDF_TEST_K1_PARTITIONED = 1, RDF_TEST_K1_RADIX = 2, RDF_TEST_K1_ATOMIC = 3 };
 enum { RDF_TEST_K2_PLAIN = 1, RDF_TEST_K2_SPLIT = 2, RDF_TEST_K2_RADIX = 3, RDF_TEST_K2_ATOMIC = 4 };
 enum { RDF_TEST_K3_ONEPASS = 1, RDF_TEST_K3_TWOPASS = 2 }; /* TWOPASS: some emission ran as count + write */
+enum { RDF_TEST_GROUPS_U64 = 1, RDF_TEST_GROUPS_KV = 2 }; /* KV: u32 joins and captures, the key-value group sort */
 
 typedef struct rdf_test_path_report {
     uint32_t k1_form, k2_form, k3_form;
@@ -136,6 +155,7 @@ typedef struct rdf_test_path_report {
     /* K3's key items (RDFIND_EMIT_KEYS) of the last group build; a rank of a sharded run reports its own */
     uint64_t k3_key_items;         /* frequent binary keys the emission took as items behind the triples (0: switch off) */
     uint64_t k3_suppressed;        /* records the triples left to those items (they still count as n_records) */
+    uint32_t group_form;           /* RDF_TEST_GROUPS_* of the last one-pass group build (RDFIND_GROUP_KV); 0: a range build */
 } rdf_test_path_report;
 
 rdf_status rdf_test_paths(rdf_ctx* ctx, rdf_test_path_report* out);

@@ -410,6 +410,162 @@ rdf_status rdf_test_group_build(rdf_ctx* c, const uint64_t* fk_host, uint64_t n,
     return RDF_OK;
 }
 
+rdf_status rdf_test_radix_pairs(rdf_ctx* c, const uint32_t* keys_host, const uint32_t* vals_host, uint64_t n, int lo, int hi,
+                                uint32_t* keys_out, uint32_t* vals_out, uint32_t* canaries_ok) {
+    if (!c) return RDF_ERR_ARG;
+    if (!canaries_ok || (n && (!keys_host || !vals_host || !keys_out || !vals_out)))
+        return fail(c, RDF_ERR_ARG, "rdf_test_radix_pairs: null argument");
+    *canaries_ok = 0;
+    if (n >= (1ull << 32) || lo < 0 || hi > 32 || hi < lo) return fail(c, RDF_ERR_ARG, "rdf_test_radix_pairs: n or bits out of range");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    TestArr ki, vi, ko, vo, kt, vt;
+    for (TestArr* a : {&ki, &vi, &ko, &vo, &kt, &vt}) HIP_TRY(c, a->make(4, n, 0, st));
+    if (n) {
+        HIP_TRY(c, hipMemcpyAsync(ki.data(), keys_host, n * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(vi.data(), vals_host, n * 4, hipMemcpyHostToDevice, st));
+    }
+    const hipError_t e = radix_sort_pairs_u32(c->ws, (const u32*)ki.data(), (const u32*)vi.data(), (u32*)ko.data(),
+                                              (u32*)vo.data(), (u32*)kt.data(), (u32*)vt.data(), n, lo, hi, st);
+    HIP_TRY(c, hipStreamSynchronize(st));
+    bool ok = true;
+    for (const TestArr* a : {&ki, &vi, &ko, &vo, &kt, &vt}) HIP_TRY(c, check_canaries(*a, &ok));
+    HIP_TRY(c, check_contents(ki, keys_host, n, &ok));  // the input is read only
+    HIP_TRY(c, check_contents(vi, vals_host, n, &ok));
+    if (n < 2 || radix_sort_passes(hi - lo) <= 1) {  // no pass or a single one: straight into the output
+        HIP_TRY(c, check_contents(kt, nullptr, n, &ok));
+        HIP_TRY(c, check_contents(vt, nullptr, n, &ok));
+    }
+    *canaries_ok = ok ? 1 : 0;
+    TRY(prim_status(c, e, "radix_sort_pairs_u32"));
+    if (n) {
+        HIP_TRY(c, hipMemcpy(keys_out, ko.data(), n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(vals_out, vo.data(), n * 4, hipMemcpyDeviceToHost));
+    }
+    return RDF_OK;
+}
+
+rdf_status rdf_test_group_kv(rdf_ctx* c, const uint64_t* keys_host, uint64_t n, int joinbits, uint64_t ncap, uint32_t ms,
+                             uint32_t V, uint32_t* support_out, uint64_t* Jf_out, uint32_t* C_out, uint64_t* doff_out,
+                             uint32_t* dgrp_out, uint64_t* G_out, uint64_t* goff_out, uint32_t* gcap_out, uint32_t* gmap_out,
+                             uint32_t* canaries_ok) {
+    if (!c) return RDF_ERR_ARG;
+    if (!canaries_ok || !support_out || !Jf_out || !C_out || !doff_out || !G_out || !goff_out || !gmap_out ||
+        (n && (!keys_host || !dgrp_out || !gcap_out)))
+        return fail(c, RDF_ERR_ARG, "rdf_test_group_kv: null argument");
+    *canaries_ok = 0;
+    *Jf_out = *G_out = 0;
+    *C_out = 0;
+    if (joinbits < 1 || joinbits > 32 || ncap < 1 || ncap >= (1ull << 31) || n >= (1ull << 32) || ms < 1 || V < 1 ||
+        (u64)V > (1ull << joinbits))
+        return fail(c, RDF_ERR_ARG, "rdf_test_group_kv: joinbits, ncap, n, ms or V out of range");
+    const u64 jm = (1ull << joinbits) - 1;
+    for (u64 i = 0; i < n; ++i)
+        if ((keys_host[i] >> joinbits) >= ncap || (keys_host[i] & jm) >= V || (i && keys_host[i] < keys_host[i - 1]))
+            return fail(c, RDF_ERR_ARG, "rdf_test_group_kv: the keys are not sorted or name a capture >= ncap or a join >= V");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const unsigned nt = (unsigned)((n + KT_TILE - 1) / KT_TILE);
+    TestArr keys, sup, tfresh, tbase, flags, fidx, skip, fcap, info, csup, doff;
+    HIP_TRY(c, keys.make(8, n, 0, st));
+    HIP_TRY(c, sup.make(4, ncap, 0, st));
+    HIP_TRY(c, tfresh.make(4, nt, 0, st));
+    HIP_TRY(c, tbase.make(4, nt + 1ull, 0, st));
+    HIP_TRY(c, flags.make(4, ncap, 0, st));
+    HIP_TRY(c, fidx.make(4, ncap + 1, 0, st));
+    HIP_TRY(c, skip.make(4, ncap + 1, 0, st));
+    if (n) HIP_TRY(c, hipMemcpyAsync(keys.data(), keys_host, n * 8, hipMemcpyHostToDevice, st));
+    const unsigned gc = grid_for(ncap, RDF_BLOCK, kGrid);
+    // the counting pass, the frequent captures' compact ids and the skip counts, as rdf_test_keep_records runs them
+    HIP_TRY(c, hipMemsetAsync(sup.data(), 0, ncap * 4, st));
+    if (nt)
+        hipLaunchKernelGGL(k_fresh_bounds, dim3(nt), dim3(RDF_BLOCK), 0, st, (const u64*)keys.data(), n, joinbits,
+                           (u32*)tfresh.data(), (u32*)sup.data());
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        e = exclusive_scan_u32(c->ws, (const u32*)tfresh.data(), (u32*)tbase.data(), nt, (u32*)tbase.data() + nt, st);
+    hipLaunchKernelGGL(k_support_flags, dim3(gc), dim3(RDF_BLOCK), 0, st, (const u32*)sup.data(), ncap, ms, (u32*)flags.data());
+    if (e == hipSuccess)
+        e = exclusive_scan_u32(c->ws, (const u32*)flags.data(), (u32*)fidx.data(), ncap, (u32*)fidx.data() + ncap, st);
+    hipLaunchKernelGGL(k_skip_counts, dim3(gc), dim3(RDF_BLOCK), 0, st, (const u32*)sup.data(), (const u32*)sup.data(), ncap, ms,
+                       (u32*)flags.data());
+    if (e == hipSuccess)
+        e = exclusive_scan_u32(c->ws, (const u32*)flags.data(), (u32*)skip.data(), ncap, (u32*)skip.data() + ncap, st);
+    u32 h[3] = {0, 0, 0};  // fresh records, those of infrequent captures, frequent captures
+    if (e == hipSuccess) e = hipMemcpyAsync(&h[0], (u32*)tbase.data() + nt, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h[1], (u32*)skip.data() + ncap, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h[2], (u32*)fidx.data() + ncap, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    TRY(prim_status(c, e, "rdf_test_group_kv (counting pass)"));
+    if (h[1] > h[0] || h[0] > n || h[2] > ncap) return fail(c, RDF_ERR_HIP, "rdf_test_group_kv: counts out of range");
+    const u64 Jf = h[0] - h[1];
+    const u32 C = h[2];
+    const unsigned ng = (unsigned)((Jf + KT_TILE - 1) / KT_TILE);
+    TestArr joins, caps, kt, vt, dgrp, gcap, theads, tgbase, goff, gmap;
+    HIP_TRY(c, fcap.make(4, C, 0, st));
+    HIP_TRY(c, info.make(sizeof(CapInfo), C, 0, st));
+    HIP_TRY(c, csup.make(4, C, 0, st));
+    HIP_TRY(c, doff.make(8, C + 1ull, 0, st));
+    for (TestArr* a : {&joins, &caps, &kt, &vt, &dgrp, &gcap}) HIP_TRY(c, a->make(4, Jf, 0, st));
+    HIP_TRY(c, theads.make(4, ng, 0, st));
+    HIP_TRY(c, tgbase.make(4, ng + 1ull, 0, st));
+    HIP_TRY(c, gmap.make(4, V, 0, st));
+    hipLaunchKernelGGL(k_compact_captures, dim3(gc), dim3(RDF_BLOCK), 0, st, (const u32*)sup.data(), (const u32*)fidx.data(), ncap,
+                       ms, (u32*)fcap.data(), (CapInfo*)info.data());
+    if (nt)
+        hipLaunchKernelGGL(k_keep_scatter_kv, dim3(nt), dim3(RDF_BLOCK), 0, st, (const u64*)keys.data(), n, joinbits,
+                           (const u32*)tbase.data(), (const u32*)skip.data(), (const u32*)sup.data(), ms, (const u32*)fidx.data(),
+                           (u32*)joins.data(), (u32*)caps.data());
+    if (C)
+        hipLaunchKernelGGL(k_info_support_u32, dim3(grid_for(C, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st,
+                           (const CapInfo*)info.data(), C, (u32*)csup.data());
+    e = hipGetLastError();
+    if (e == hipSuccess)
+        e = exclusive_scan_u32_u64(c->ws, (const u32*)csup.data(), (u64*)doff.data(), C, (u64*)doff.data() + C, st);
+    // the pair sort (the sorted joins into dgrp, the sorted captures into gcap) and the group passes (g_compact_groups)
+    if (e == hipSuccess)
+        e = radix_sort_pairs_u32(c->ws, (const u32*)joins.data(), (const u32*)caps.data(), (u32*)dgrp.data(), (u32*)gcap.data(),
+                                 (u32*)kt.data(), (u32*)vt.data(), Jf, 0, joinbits, st);
+    if (ng) hipLaunchKernelGGL(k_group_flags_kv, dim3(ng), dim3(RDF_BLOCK), 0, st, (const u32*)dgrp.data(), Jf, (u32*)theads.data());
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess)
+        e = exclusive_scan_u32(c->ws, (const u32*)theads.data(), (u32*)tgbase.data(), ng, (u32*)tgbase.data() + ng, st);
+    u32 G = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&G, (u32*)tgbase.data() + ng, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    TRY(prim_status(c, e, "rdf_test_group_kv (group heads)"));
+    if (G > Jf) return fail(c, RDF_ERR_HIP, "rdf_test_group_kv: more groups than records");
+    HIP_TRY(c, goff.make(8, G + 1ull, 0, st));
+    if (ng) {
+        hipLaunchKernelGGL(k_group_build_kv, dim3(ng), dim3(RDF_BLOCK), 0, st, (const u32*)dgrp.data(), Jf,
+                           (const u32*)tgbase.data(), (u64*)goff.data(), (u32*)gmap.data());
+        hipLaunchKernelGGL(k_dgrp_kv, dim3(grid_for(Jf, RDF_BLOCK, kGrid)), dim3(RDF_BLOCK), 0, st, (const u32*)joins.data(), Jf,
+                           (const u32*)gmap.data(), (u32*)dgrp.data());
+    }
+    e = hipGetLastError();
+    HIP_TRY(c, hipMemcpyAsync((u64*)goff.data() + G, &Jf, 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    bool ok = true;
+    for (const TestArr* a : {&keys, &sup, &tfresh, &tbase, &flags, &fidx, &skip, &fcap, &info, &csup, &doff, &joins, &caps, &kt,
+                             &vt, &dgrp, &gcap, &theads, &tgbase, &goff, &gmap})
+        HIP_TRY(c, check_canaries(*a, &ok));
+    HIP_TRY(c, check_contents(keys, keys_host, n, &ok));  // the records are read only
+    *canaries_ok = ok ? 1 : 0;
+    TRY(prim_status(c, e, "rdf_test_group_kv"));
+    HIP_TRY(c, hipMemcpy(support_out, sup.data(), ncap * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(doff_out, doff.data(), (C + 1ull) * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(goff_out, goff.data(), (G + 1ull) * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(gmap_out, gmap.data(), (u64)V * 4, hipMemcpyDeviceToHost));
+    if (Jf) {
+        HIP_TRY(c, hipMemcpy(dgrp_out, dgrp.data(), Jf * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(gcap_out, gcap.data(), Jf * 4, hipMemcpyDeviceToHost));
+    }
+    *Jf_out = Jf;
+    *C_out = C;
+    *G_out = G;
+    return RDF_OK;
+}
+
 rdf_status rdf_test_paths(rdf_ctx* c, rdf_test_path_report* out) {
     if (!c || !out) return RDF_ERR_ARG;
     if (c->stage < 4) return fail(c, RDF_ERR_STATE, "no completed run");
@@ -438,6 +594,7 @@ rdf_status rdf_test_paths(rdf_ctx* c, rdf_test_path_report* out) {
     r.k3_hist = c->k3_hist ? 1 : 0;
     r.k3_key_items = c->k3_key_items;
     r.k3_suppressed = c->k3_suppressed;
+    r.group_form = c->path_group_kv;
     r.hclassed = c->hclassed ? 1 : 0;
     r.n_emit_tiles = c->pend_NT;
     // the class lists as the run left them: class m's is lists[lwoff[cchoff[m]], lwoff[cchoff[m + 1]]).  n_classes and
